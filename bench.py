@@ -1,17 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark: baseband -> filterbank throughput of the HIP hot path on MI355X.
 
-Contract:  python bench.py --gpus N --steps K --warmup W
+Contract:  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N = 1   one antenna, 128 MS/s dual-pol, RFI mode 2 (raw + excised streams), 8-bit out
           (BASELINE.json configs[1]).  A *step* = one second of that antenna
           (10 segments x 1024 FFT rows x 12500 samples x 2 pols = 256 MB of 8-bit voltages)
           through kurtosis flagging -> channeliser -> detect/scrunch/quantise, with the raw
           samples already resident in HBM and the filterbank bytes copied back to the host.
-          The same JSON line carries sub-records measured right after the headline run:
+          With --full the same JSON line carries sub-records measured right after the headline run:
             taps4   the same step with the 4-tap polyphase window (north_star's PFB);
             ingest  the same step with every second arriving from page-locked host memory as VDIF
                     frames through pb_submit_vdif (PCIe-inclusive; never `value`);
-            search  one heimdall-sized gulp of the downstream dedispersion + boxcar search.
+            search  one heimdall-sized gulp of the downstream dedispersion + boxcar search;
+          and the CPU baseline, the cold region, the kernels alone, power / residency / VALU figures.
   N > 1   one rank per GPU: either a launcher has started them already (torch.distributed.run sets
           WORLD_SIZE, which must equal N) or `python bench.py --gpus N` starts them itself as child
           processes under torch.distributed.run before anything touches the GPU and relays rank 0's line and
@@ -19,9 +20,12 @@ Contract:  python bench.py --gpus N --steps K --warmup W
           GPU (weak scaling) and the per-step incoherent sum of the excised fp32 planes is an RCCL reduce to
           rank 0 over xGMI, which requantises the coadded second; the line then carries `rccl_ranks`, and at
           N = 8 a `configs3` sub-record (BASELINE configs[3]: 16 antennas, 2 per GPU).
-Timing: W warm-up steps + K timed steps straight after set-up give `ms_per_step_cold`; then 100 untimed
-steps, W warm-up steps and `--regions` (5) back-to-back regions of exactly K steps each, every one bracketed by
-barrier + synchronise, MAX over ranks: `ms_per_step` / `value` are the MEDIAN region, min and max beside it.
+Timing: 100 untimed steps and W warm-up steps, then `--regions` back-to-back regions of exactly K steps each,
+every one bracketed by barrier + synchronise, MAX over ranks: `ms_per_step` / `value` are the MEDIAN region, min
+and max beside it.  A plain run times ONE region (K timed steps in all); --full times five by default and, before
+them, W warm-up steps + K timed steps straight after set-up (`ms_per_step_cold`).
+--dump-outputs DIR: after the timed steps, the filterbank codes the headline run's last step handed to the host
+(rank 0's antennas, every output stream) as DIR/<name>.npy in float32, 64 MB at most (write_outputs).
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -77,6 +81,28 @@ def synth_second(torch, dev, seed, seg_samples, nseg, rfi_frac=0.0):
             pols.append(x.clamp_(0, 255).to(torch.uint8))
         out.append(pols)
     return out
+
+
+DUMP_BUDGET_BYTES = 63_000_000      # float32 payload of --dump-outputs: with the .npy headers, under 64 MB in all
+
+
+def write_outputs(outdir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """arrays {name: ndarray} -> outdir/<name>.npy in float32.  When they would take more than `budget` bytes, every
+    array is cut to the same share of its elements, taken at positions drawn from a generator seeded with `seed`
+    (sorted, flattened): the same shapes give the same positions in every run.  -> {name: (shape written, sampled)}"""
+    os.makedirs(outdir, exist_ok=True)
+    total = sum(a.size for a in arrays.values()) * 4
+    rng = np.random.default_rng(seed)
+    written = {}
+    for name in sorted(arrays):
+        a = np.asarray(arrays[name], dtype=np.float32)
+        sampled = total > budget
+        if sampled:
+            keep = a.size * budget // total
+            a = a.ravel()[np.sort(rng.choice(a.size, keep, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        written[name] = (a.shape, sampled)
+    return written
 
 
 # ---------------------------------------------------------------------------------------------
@@ -444,13 +470,14 @@ def algorithmic_bytes(args, h, n, world, taps):
 
 
 def run_chain(torch, dist, lp, args, dev, local, rank, world, taps, steps, warmup, ingest=False, coadd=None,
-              ant_per_gpu=None, regions=None):
-    """One measurement of the pipeline: a COLD timed region (the caller's W warm-up steps, then K timed steps, on a
-    GPU that has just been set up: what the driver's literal command sees without preconditioning), then
-    PRECONDITION_STEPS untimed steps + W warm-up steps and `regions` back-to-back timed regions of exactly K steps
+              ant_per_gpu=None, regions=None, cold=True, dump=False):
+    """One measurement of the pipeline: with `cold`, a COLD timed region first (the caller's W warm-up steps, then K
+    timed steps, on a GPU that has just been set up: what a short run sees without preconditioning);
+    then PRECONDITION_STEPS untimed steps + W warm-up steps and `regions` back-to-back timed regions of exactly K steps
     each (every one bracketed by barrier + synchronise on both sides, MAX over ranks).  ms_per_step = the median
     region; min / max are reported beside it.  ingest: every second arrives as VDIF frames from page-locked host
-    memory (pb_submit_vdif), otherwise the samples are resident in HBM."""
+    memory (pb_submit_vdif), otherwise the samples are resident in HBM.  dump: rank 0's result carries `outputs`,
+    the filterbank codes of the last timed step as the host received them ({name: uint8 array (segments, bytes)})."""
     S = args.seg_per_step
     A = args.ant_per_gpu if ant_per_gpu is None else ant_per_gpu
     regions = args.regions if regions is None else regions
@@ -580,10 +607,12 @@ def run_chain(torch, dist, lp, args, dev, local, rank, world, taps, steps, warmu
             dt = max(per_rank[-1])
         return dt
 
-    for _ in range(warmup):
-        step()
-    fence()
-    dt_cold = timed_region()
+    dt_cold = None
+    if cold:
+        for _ in range(warmup):
+            step()
+        fence()
+        dt_cold = timed_region()
     for _ in range(PRECONDITION_STEPS + warmup):
         step()
     fence()
@@ -594,6 +623,12 @@ def run_chain(torch, dist, lp, args, dev, local, rank, world, taps, steps, warmu
         leg.reduce_ms()
         leg.timing = True
     dts = [timed_region() for _ in range(max(1, regions))]
+    outputs = None
+    if dump and rank == 0:
+        # the fence drained every batch: the last timed step (k = steps - 1 of the region) sits in its set's pinned mirror
+        h.select_set((steps - 1) % NSETS)
+        outputs = {"filterbank_%s_ant%d" % ("raw" if st == 0 else "kur", a): h.fetch_view(a, st, S).reshape(S, h.trim).copy()
+                   for a in range(A) for st in nstream_out}
     red_ms, red_n = leg.reduce_ms() if leg is not None else (0.0, 0)
     gc.enable()
     dt = float(np.median(dts))
@@ -619,7 +654,7 @@ def run_chain(torch, dist, lp, args, dev, local, rank, world, taps, steps, warmu
         per_launch = alg[dom] * S * A
         achieved = per_launch / (avg_ms * 1e-3) / 1e9
         res = {"msamp": msamp, "ms_per_step": dt / steps * 1e3, "nant_total": nant_total, "ant_per_gpu": A,
-               "ms_per_step_cold": dt_cold / steps * 1e3,
+               "ms_per_step_cold": dt_cold / steps * 1e3 if dt_cold is not None else None, "outputs": outputs,
                "regions": {"n": len(dts), "steps_each": steps, "ms_per_step_median": round(dt / steps * 1e3, 4),
                            "ms_per_step_min": round(min(dts) / steps * 1e3, 4),
                            "ms_per_step_max": round(max(dts) / steps * 1e3, 4)},
@@ -730,8 +765,15 @@ def build_parser():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--regions", type=int, default=5,
-                    help="back-to-back timed regions of --steps steps each (median reported, min / max beside it)")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="back-to-back timed regions of --steps steps each (median reported, min / max beside it; "
+                         "default 1, with --full or --coadd-selftest 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the cold region, the CPU baseline, the kernels alone, power, "
+                         "residency and VALU figures, the taps4 / ingest / search / configs3 sub-records (the --no-* "
+                         "options below leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the filterbank codes of the headline run's last timed step to DIR/<name>.npy (float32)")
     ap.add_argument("--backend", choices=["lds", "hipfft"], default="lds")
     ap.add_argument("--rfi-mode", type=int, default=2)
     ap.add_argument("--nbit", type=int, default=8)
@@ -768,6 +810,15 @@ def build_parser():
                     help="N = 1 only: print the step with the incoherent-sum leg of the N > 1 path switched on "
                          "(fp32 planes kept, local sum, RCCL reduce in a one-rank group, requantisation) instead of the bench line")
     return ap
+
+
+def parse_args(argv):
+    """the parser's namespace with the defaults that depend on other options filled in: a plain run times exactly
+    --steps steps (one region)"""
+    args = build_parser().parse_args(argv)
+    if args.regions is None:
+        args.regions = 5 if args.full or args.coadd_selftest else 1
+    return args
 
 
 def launcher_argv(args, argv, port):
@@ -822,7 +873,7 @@ def launch_ranks(args, argv, run=None):
 
 def main():
     argv = sys.argv[1:]
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if args.dist_backend == "threads" and args.gpus > 1:
@@ -839,7 +890,7 @@ def main():
         raise SystemExit("bench.py: --gpus %d but the launcher started %d rank(s)" % (args.gpus, world))
     # the CPU baseline forks a process pool: before torch / HIP are initialised in this process
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline()
 
     import torch
@@ -908,11 +959,12 @@ def rank_body(args, rank, world, local, cpu, torch, dist, dev, ndev):
                                              "stage_ms_per_step": withc["stage_ms_per_step"]}}))
         dist.destroy_process_group()
         return
-    r = run_chain(torch, dist, lp, args, dev, local, rank, world, args.taps, args.steps, args.warmup)
+    r = run_chain(torch, dist, lp, args, dev, local, rank, world, args.taps, args.steps, args.warmup, cold=args.full,
+                  dump=bool(args.dump_outputs))
     # BASELINE configs[3] on the whole node: 16 antennas = 2 per GPU on 8 GPUs (every rank takes part)
     c3 = None
     c3_at = int(os.environ.get("PB_BENCH_CONFIGS3_AT", "8"))      # (rehearsals: the world size that adds the sub-record)
-    if world == c3_at and world > 1 and A == 1 and not args.no_extras and args.taps == 1:
+    if args.full and world == c3_at and world > 1 and A == 1 and not args.no_extras and args.taps == 1:
         c3 = run_chain(torch, dist, lp, args, dev, local, rank, world, 1, args.steps, args.warmup, ant_per_gpu=2)
 
     if rank == 0:
@@ -924,7 +976,7 @@ def rank_body(args, rank, world, local, cpu, torch, dist, dev, ndev):
             "metric": "Msamp/s/antenna (dual-pol) and x real-time @128 MS/s; % HBM roofline",
             "value": round(msamp, 1), "unit": "Msamp/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "precondition_steps": PRECONDITION_STEPS, "ms_per_step": round(r["ms_per_step"], 4),
-            "ms_per_step_cold": round(r["ms_per_step_cold"], 4), "timed_regions": r["regions"],
+            "timed_regions": r["regions"], "full": args.full,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
             "data": "synthetic genbase-style 8-bit Gaussian baseband (mean 128.5, sigma 16.9 codes), "
                     "%g%% of 500-sample blocks with impulsive RFI; resident in HBM" % (100 * args.rfi_frac),
@@ -936,10 +988,12 @@ def rank_body(args, rank, world, local, cpu, torch, dist, dev, ndev):
                                                                         else "+rccl-reduce-coadd") if world > 1 else "")},
             "msamp_per_antenna": round(msamp / nant_total, 1),
             "x_realtime_per_antenna": round(msamp / nant_total / 128.0, 1),
-            "x_realtime_per_antenna_cold": round(msamp / nant_total / 128.0 * r["ms_per_step"] / r["ms_per_step_cold"], 1),
             "roofline": r["roofline"],
             "stage_ms_per_step": r["stage_ms_per_step"],
         }
+        if args.full:
+            out["ms_per_step_cold"] = round(r["ms_per_step_cold"], 4)
+            out["x_realtime_per_antenna_cold"] = round(msamp / nant_total / 128.0 * r["ms_per_step"] / r["ms_per_step_cold"], 1)
         if world > 1:
             out["rccl_ranks"] = dist.get_world_size()
             out["dist_backend"] = "%s (%s)" % (dist.get_backend(), "RCCL" if args.dist_backend == "nccl" else "rehearsal")
@@ -976,7 +1030,7 @@ def rank_body(args, rank, world, local, cpu, torch, dist, dev, ndev):
                                                             "its share, codes gathered" if c3.get("coadd_layout") == "sliced"
                                                             else "local tree, gather, root tree") if args.coadd_order == "tree"
                                                            else "local sum, one reduce")}
-        if world == 1:
+        if args.full and world == 1:
             try:
                 out["roofline"]["alone"] = alone_record(torch, lp, args, dev, local, args.taps)
             except Exception as e:
@@ -992,7 +1046,7 @@ def rank_body(args, rank, world, local, cpu, torch, dist, dev, ndev):
                 out["roofline"]["valu"] = valu_record(args, args.taps, r["ms_per_step"], pw.get("gfx_mhz"))
             except Exception as e:
                 out["roofline"]["valu"] = {"error": str(e)}
-        if world == 1 and not args.no_extras and args.taps == 1 and A == 1:
+        if args.full and world == 1 and not args.no_extras and args.taps == 1 and A == 1:
             nsub = max(20, 2 * args.steps // 3)      # (short runs time the pipeline's fill and drain)
             t4 = run_chain(torch, dist, lp, args, dev, local, rank, world, 4, nsub, min(args.warmup, 5))
             out["taps4"] = {"ms_per_step": round(t4["ms_per_step"], 4), "ms_per_step_cold": round(t4["ms_per_step_cold"], 4),
@@ -1019,6 +1073,8 @@ def rank_body(args, rank, world, local, cpu, torch, dist, dev, ndev):
                 out["search"] = {"error": str(e)}
         if cpu is not None:
             out["cpu_baseline"] = cpu
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, r["outputs"])
         print(json.dumps(out))
 
 

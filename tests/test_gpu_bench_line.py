@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +25,7 @@ def _run(*flags, timeout=600):
 def test_bench_line_fields_and_consistency():
     # (--no-residency: the in-run co-runner probe loads the EXPERIMENTS build in a child process; the test suite runs
     #  the product library only -- the probe has a test of its own below, off unless asked for)
-    d = _run("--steps", "6", "--warmup", "2", "--regions", "2", "--no-extras", "--no-residency")
+    d = _run("--full", "--steps", "6", "--warmup", "2", "--regions", "2", "--no-extras", "--no-residency")
     assert d["metric"].startswith("Msamp/s/antenna") and d["unit"] == "Msamp/s" and d["higher_is_better"] is True
     assert d["n_gpus"] == 1 and d["steps"] == 6 and d["warmup"] == 2 and d["scaling"] == "weak" and d["vs_baseline"] is None
     assert "configs[1]" in d["config"]["workload"] and "model" not in d["config"]
@@ -62,6 +63,32 @@ def test_bench_line_fields_and_consistency():
     assert hp["kind"] == "port" and hp["cores"] == 1 and 1 < hp["value"] < c["value_1core"] * 2 and "configs[1]" in hp["sample"]
 
 
+def test_plain_run_times_exactly_its_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full: set-up, warm-up, ONE region of exactly --steps steps and the headline fields, nothing that
+    takes a run of its own.  --dump-outputs: the last step's filterbank codes of both streams as float32 .npy, the
+    same in two runs with the same arguments."""
+    dumps = []
+    for i in range(2):
+        d = _run("--gpus", "1", "--steps", "5", "--warmup", "2", "--dump-outputs", str(tmp_path / str(i)))
+        assert d["metric"].startswith("Msamp/s/antenna") and d["unit"] == "Msamp/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f32" and d["full"] is False and d["steps"] == 5 and d["warmup"] == 2
+        tr = d["timed_regions"]
+        assert tr["n"] == 1 and tr["steps_each"] == 5 and tr["ms_per_step_median"] == d["ms_per_step"] > 0
+        assert abs(d["value"] - 128e6 / (d["ms_per_step"] * 1e-3) / 1e6) / d["value"] < 1e-3
+        assert not {"ms_per_step_cold", "cpu_baseline", "taps4", "ingest", "search"} & set(d)
+        assert not {"alone", "power", "residency", "valu"} & set(d["roofline"]) and d["roofline"]["kernel"] == "channelize"
+        files = sorted(os.listdir(str(tmp_path / str(i))))
+        assert files == ["filterbank_kur_ant0.npy", "filterbank_raw_ant0.npy"]
+        arrs = [np.load(str(tmp_path / str(i) / f)) for f in files]
+        for a in arrs:
+            assert a.dtype == np.float32 and a.ndim == 2 and a.shape[0] == 10
+            assert a.min() >= 0 and a.max() <= 255 and np.array_equal(a, np.round(a)) and a.std() > 0
+        assert sum(a.nbytes for a in arrs) <= 64_000_000
+        dumps.append(arrs)
+    for a, b in zip(*dumps):
+        assert np.array_equal(a, b)
+
+
 @pytest.mark.skipif(os.environ.get("PB_TEST_EXPERIMENTS_BUILD") != "1",
                     reason="loads libpb_hip_exp.so in a child process: only on request (PB_TEST_EXPERIMENTS_BUILD=1)")
 def test_bench_measures_residency_in_run_with_the_experiments_build():
@@ -69,7 +96,7 @@ def test_bench_measures_residency_in_run_with_the_experiments_build():
     build/libcorun.so are in the tree and as new as the kernel sources; quoted from a committed record of THESE kernel
     sources otherwise; absent else.  Only a measurement is asserted on (a quote is a committed file compared with
     itself)."""
-    d = _run("--steps", "6", "--warmup", "2", "--regions", "1", "--no-extras", "--no-cpu-baseline", "--no-power")
+    d = _run("--full", "--steps", "6", "--warmup", "2", "--regions", "1", "--no-extras", "--no-cpu-baseline", "--no-power")
     rs = d["roofline"]["residency"]
     assert rs is not None and "error" not in rs, rs
     assert rs["kernel_source_sha16"] and rs["measured_in_run"] is True, rs

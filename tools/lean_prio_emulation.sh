@@ -5,7 +5,7 @@
 # (leand10 / leand20).   needs: tools/build_variant_multi.sh lean "-DFFT_LEAN" k_channelize.hip
 #   tools/build_variant_multi.sh leanp3 "-DFFT_LEAN -DD2_PRIO_B=3" k_channelize.hip k_detect2.hip
 #   tools/build_variant_multi.sh leand10 "-DFFT_LEAN -DPB_CHAN_DELAY_US=10" k_channelize.hip pb_api.hip
-run() { python bench.py --steps 40 --warmup 5 --regions 3 --no-extras --no-cpu-baseline --no-power --no-residency 2>/dev/null | python -c "
+run() { python bench.py --full --steps 40 --warmup 5 --regions 3 --no-extras --no-cpu-baseline --no-power --no-residency 2>/dev/null | python -c "
 import sys,json
 d=json.loads([l for l in sys.stdin if l.startswith('{')][0]); print(d['ms_per_step'], d['timed_regions']['ms_per_step_min'], d['timed_regions']['ms_per_step_max'], d['stage_ms_per_step'], 'alone', d['roofline'].get('alone', {}).get('ms_per_launch'))"; }
 export PB_FUSE_KURTOSIS=0

@@ -9,9 +9,9 @@ tests)
   timeout -k 10 900 python -m pytest tests -m gpu -q > $O/t_all.log 2>&1 || { tail -40 $O/t_all.log; exit 1; }
   tail -2 $O/t_all.log ;;
 bench)
-  timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
-  timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --ant-per-gpu 2 --no-cpu-baseline --no-extras > $O/bench_two_antennas.json 2> $O/bench_two_antennas.err
+  timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
+  timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --ant-per-gpu 2 --no-cpu-baseline --no-extras > $O/bench_two_antennas.json 2> $O/bench_two_antennas.err
   python - <<'PY'
 import json
 for f in ("bench_driver_cmd", "bench", "bench_two_antennas"):
@@ -22,10 +22,10 @@ PY
   ;;
 rehearse)
   # configs[3]'s real shape on the one card: eight ranks as threads of one process (the pool allows six PROCESSES on a card)
-  timeout -k 10 600 python bench.py --gpus 8 --share-gpus --dist-backend threads --steps 5 --warmup 2 > $O/threads8_configs3_rehearsal.json 2> $O/threads8.err || { tail -20 $O/threads8.err; exit 1; }
-  timeout -k 10 600 python bench.py --gpus 8 --share-gpus --dist-backend threads --coadd-layout root --steps 5 --warmup 2 --no-extras > $O/threads8_root_layout.json 2> $O/threads8_root.err
-  PB_BENCH_CONFIGS3_AT=4 timeout -k 10 600 python bench.py --gpus 4 --share-gpus --dist-backend gloo --steps 5 --warmup 2 > $O/gloo4_configs3_rehearsal.json 2> $O/gloo4.err
-  timeout -k 10 600 python bench.py --gpus 2 --share-gpus --dist-backend gloo --steps 5 --warmup 2 > $O/gloo2_launcher.json 2> $O/gloo2.err
+  timeout -k 10 600 python bench.py --full --gpus 8 --share-gpus --dist-backend threads --steps 5 --warmup 2 > $O/threads8_configs3_rehearsal.json 2> $O/threads8.err || { tail -20 $O/threads8.err; exit 1; }
+  timeout -k 10 600 python bench.py --full --gpus 8 --share-gpus --dist-backend threads --coadd-layout root --steps 5 --warmup 2 --no-extras > $O/threads8_root_layout.json 2> $O/threads8_root.err
+  PB_BENCH_CONFIGS3_AT=4 timeout -k 10 600 python bench.py --full --gpus 4 --share-gpus --dist-backend gloo --steps 5 --warmup 2 > $O/gloo4_configs3_rehearsal.json 2> $O/gloo4.err
+  timeout -k 10 600 python bench.py --full --gpus 2 --share-gpus --dist-backend gloo --steps 5 --warmup 2 > $O/gloo2_launcher.json 2> $O/gloo2.err
   python - <<'PY'
 import json
 for f in ("threads8_configs3_rehearsal", "threads8_root_layout", "gloo4_configs3_rehearsal", "gloo2_launcher"):

@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/ws_$1; shift
 rm -rf $OUT; mkdir -p $OUT
 for c in WRITE_SIZE FETCH_SIZE; do
-rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/$c -- python3 bench.py --steps 8 --warmup 4 --regions 1 --no-cpu-baseline --no-extras --no-power "$@" > /dev/null 2> $OUT/$c.err
+rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/$c -- python3 bench.py --full --steps 8 --warmup 4 --regions 1 --no-cpu-baseline --no-extras --no-power "$@" > /dev/null 2> $OUT/$c.err
 python3 - $OUT/$c $c <<'PY'
 import csv, glob, sys, collections
 acc = collections.defaultdict(list)
