@@ -57,7 +57,8 @@ extern "C" {
 typedef struct pb_handle pb_handle;
 
 typedef struct pb_config {
-    uint32_t struct_size;   /* sizeof(pb_config), for ABI growth */
+    uint32_t struct_size;   /* sizeof(pb_config), for ABI growth (pb_create also takes the size without `coherence`:
+                               callers built before it was appended get coherence = 0) */
     int32_t device;         /* -g   src/process_baseband.cu:458-472 */
     int32_t nant;           /* antennas batched on this GPU (reference: one process each) */
     int32_t nbit;           /* -b   2 | 4 | 8              :416-425 */
@@ -74,13 +75,28 @@ typedef struct pb_config {
                              * pair; without it the in-library-FFT channeliser flags its own rows: same results) */
     int32_t nsets;          /* buffer sets for batch pipelining, 1..8 (1 = none, 2 = double-buffered, 3 = the host
                              * collects the batch queued two calls ago) */
+    int32_t coherence;      /* 1 = coherence output (needs npol = 2), 0 = off */
 } pb_config;
+
+/* Coherence output (coherence = 1, "-P 2 --coherence"): per output time sample [time][4][4096] in the order
+ * AA, BB, CR, CI (the AABBCRCI coherence products).  Pol A = VDIF thread 0, pol B = thread 1, row t of each.
+ * AA and BB are byte for byte what npol = 2 writes.  With A = (ax, ay), B = (bx, by) the complex in-band spectra
+ * of the row (after injection), every line one binary32 operation, left to right, no contraction:
+ *   re = ax*bx + ay*by          im = ay*bx - ax*by     (im = Im(A conj B): swapping the pols negates CI)
+ *   raw stream:     n = bpA' * bpB'                       (bandpass after this row's update, as AA / BB divide by)
+ *   excised stream: n = (bpA' * wA) * (bpB' * wB)         (row weights after apply_kurtosis); CR = CI = 0 if
+ *                   either weight is 0 or either pol's power takes the 11x clip
+ *   d = sqrtf(n);  CR = re / d * 1.41421356f;  CI = im / d * 1.41421356f
+ * Time scrunch: raw = tscrunch (sum of 8 rows, * (float)sqrt(1./8)); excised = tscrunch_weights with the row
+ * weight (float)(0.5 * (wA + wB)) when both weights are >= 0.2, else the row is skipped.  The 8/4/2-bit quantisers
+ * with npol = 4.  code_bytes_per_seg = 4 * R/8 * 4096 * nbit/8, ave_floats_per_seg = 4 * R/8 * 4096 (compact
+ * [4][R/8][4096]).  Not offered (PB_EINVAL): taps = 4, PB_FFT_HIPFFT, debug_keep, the pb_coadd_* entry points. */
 
 typedef struct pb_sizes {
     uint64_t seg_samples_per_pol;  /* rows_per_seg * 12500 */
     uint64_t input_bytes_per_seg;  /* 2 * seg_samples_per_pol */
     uint64_t code_bytes_per_seg;   /* "trim", src/process_baseband.cu:667-675 */
-    uint64_t ave_floats_per_seg;   /* compact: (npol==1?1:2) * rows_per_seg/8 * 4096 */
+    uint64_t ave_floats_per_seg;   /* compact: (npol==1?1:2, coherence: 4) * rows_per_seg/8 * 4096 */
     uint64_t rows_per_seg;
     uint64_t blocks_per_seg_pol;   /* rows_per_seg * 25 kurtosis blocks */
     uint64_t device_bytes;         /* HBM held by the handle */

@@ -124,6 +124,7 @@ hipError_t launch_detect(pb_handle *h, int nseg, int)
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
+    if (h->cfg.coherence) return launch_detect_coh(h, nseg);
     return launch_detect_pow(h, nseg);
 }
 

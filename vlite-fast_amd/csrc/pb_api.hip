@@ -119,6 +119,7 @@ extern "C" void pb_config_default(pb_config *c)
     c->keep_ave = 0;
     c->debug_keep = 0;
     c->nsets = 1;
+    c->coherence = 0;
 }
 
 // D'Agostino constants with the reference's float/double evaluation (src/pb_kernels.cu:4-11)
@@ -368,8 +369,9 @@ static int create_impl(pb_handle *h)
         if (need_kur) HIPCHK(h, dmalloc(h, &h->d_Xkur, xn));
     }
     {
-        // power planes: written by the LDS channeliser, or from the complex spectra of hipFFT
-        const size_t pn = A * S * 2 * R * PB_NCHANOUT;
+        // power planes: written by the LDS channeliser, or from the complex spectra of hipFFT; coherence output:
+        // the complex in-band spectra (float2) in their place
+        const size_t pn = A * S * 2 * R * PB_NCHANOUT * (c.coherence ? 2 : 1);
         if (need_raw) HIPCHK(h, dmalloc(h, &h->d_Praw, pn));
         if (need_kur) HIPCHK(h, dmalloc(h, &h->d_Pkur, pn));
     }
@@ -456,8 +458,16 @@ extern "C" int pb_create(const pb_config *cfg, pb_handle **out)
 {
     if (!cfg || !out) return fail(nullptr, PB_EINVAL, "pb_create: null argument");
     *out = nullptr;
-    if (cfg->struct_size != sizeof(pb_config)) return fail(nullptr, PB_EINVAL, "pb_create: pb_config size mismatch");
-    const pb_config &c = *cfg;
+    // a caller built against the header before `coherence` was appended passes the shorter struct: the fields it
+    // does not have take their defaults (0)
+    const size_t before_coherence = offsetof(pb_config, coherence);
+    if (cfg->struct_size != sizeof(pb_config) && cfg->struct_size != before_coherence)
+        return fail(nullptr, PB_EINVAL, "pb_create: pb_config size mismatch");
+    pb_config grown;
+    memset(&grown, 0, sizeof grown);
+    memcpy(&grown, cfg, cfg->struct_size);
+    grown.struct_size = sizeof grown;
+    const pb_config &c = grown;
     if (!(c.nbit == 2 || c.nbit == 4 || c.nbit == 8)) return fail(nullptr, PB_EINVAL, "Unsupported NBIT!");
     if (!(c.npol == 1 || c.npol == 2)) return fail(nullptr, PB_EINVAL, "Unsupported npol!");
     if (c.rfi_mode < 0 || c.rfi_mode > 2) return fail(nullptr, PB_EINVAL, "Unsupported RFI mode!");
@@ -467,6 +477,14 @@ extern "C" int pb_create(const pb_config *cfg, pb_handle **out)
     if (c.nant < 1 || c.max_seg < 1) return fail(nullptr, PB_EINVAL, "nant and max_seg must be >= 1");
     if (c.nsets < 1 || c.nsets > 8) return fail(nullptr, PB_EINVAL, "nsets must be 1..8");
     if (c.rows_per_seg < 8 || c.rows_per_seg % PB_NSCRUNCH) return fail(nullptr, PB_EINVAL, "rows_per_seg must be a positive multiple of 8");
+    if (!(c.coherence == 0 || c.coherence == 1)) return fail(nullptr, PB_EINVAL, "coherence must be 0 or 1");
+    if (c.coherence) {
+        // coherence output: AA, BB, CR, CI; what it is not built for is refused
+        if (c.npol != 2) return fail(nullptr, PB_EINVAL, "coherence output needs npol = 2 (-P 2 --coherence)");
+        if (c.taps != 1) return fail(nullptr, PB_EINVAL, "coherence output is not implemented for taps = 4 (PFB)");
+        if (c.fft_backend != PB_FFT_LDS) return fail(nullptr, PB_EINVAL, "coherence output needs the LDS FFT back end, not hipFFT");
+        if (c.debug_keep) return fail(nullptr, PB_EINVAL, "coherence output is not implemented with debug_keep = 1");
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, PB_EHIP, "pb_create: no HIP device (libpb_hip has no CPU fallback)");
@@ -484,6 +502,11 @@ extern "C" int pb_create(const pb_config *cfg, pb_handle **out)
     const int polfac = c.npol == 1 ? 2 : 1;
     h->trim = (size_t)2 * h->R * PB_NCHANOUT / (polfac * PB_NSCRUNCH) / (8 / c.nbit);
     h->ave_per_seg = (size_t)2 * h->R * PB_NCHANOUT / (polfac * PB_NSCRUNCH);
+    if (c.coherence) {
+        // four products per output sample: [time][AA, BB, CR, CI][4096]
+        h->trim = (size_t)4 * (h->R / PB_NSCRUNCH) * PB_NCHANOUT * c.nbit / 8;
+        h->ave_per_seg = (size_t)4 * (h->R / PB_NSCRUNCH) * PB_NCHANOUT;
+    }
     h->stream = nullptr;
     h->own_stream = false;
     h->device_bytes = 0;
@@ -1186,9 +1209,17 @@ extern "C" int pb_set_coadd_stream(pb_handle *h, void *stream)
     return PB_OK;
 }
 
+// The incoherent sum is defined on the one-pol (AA+BB) planes: coherence output does not take part in it.
+static int no_coherence(pb_handle *h, const char *what)
+{
+    if (!h->cfg.coherence) return PB_OK;
+    return fail(h, PB_EINVAL, std::string(what) + ": the coadd entry points do not take coherence output (npol = 1 only)");
+}
+
 extern "C" int pb_coadd_local(pb_handle *h, int nseg, float *d_sum, int accumulate)
 {
     if (!h || !d_sum) return PB_EINVAL;
+    if (int rc = no_coherence(h, "pb_coadd_local")) return rc;
     if (!h->cfg.keep_ave) return fail(h, PB_ESTATE, "pb_coadd_local needs keep_ave=1");
     if (nseg < 1 || nseg > h->S) return fail(h, PB_EINVAL, "pb_coadd_local: nseg out of range");
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -1226,6 +1257,7 @@ hipError_t launch_coadd_local_codes(pb_handle *h, int nseg, float *d_sum, int ac
 extern "C" int pb_coadd_local_codes(pb_handle *h, int nseg, float *d_sum, int accumulate)
 {
     if (!h || !d_sum) return PB_EINVAL;
+    if (int rc = no_coherence(h, "pb_coadd_local_codes")) return rc;
     if (nseg < 1 || nseg > h->S) return fail(h, PB_EINVAL, "pb_coadd_local_codes: nseg out of range");
     if (nseg > h->processed) return fail(h, PB_EINVAL, "pb_coadd_local_codes: more segments than the batch holds");
     if (h->d_coadd_target && d_sum == h->d_coadd_target)
@@ -1268,6 +1300,7 @@ extern "C" int pb_coadd_tree_order(int n, int32_t *order)
 extern "C" int pb_coadd_local_tree(pb_handle *h, int nseg, const int32_t *ant_order, int n, float *d_dst)
 {
     if (!h || !d_dst || !ant_order) return PB_EINVAL;
+    if (int rc = no_coherence(h, "pb_coadd_local_tree")) return rc;
     if (!h->cfg.keep_ave) return fail(h, PB_ESTATE, "pb_coadd_local_tree needs keep_ave=1");
     if (nseg < 1 || nseg > h->S) return fail(h, PB_EINVAL, "pb_coadd_local_tree: nseg out of range");
     if (nseg > h->processed) return fail(h, PB_EINVAL, "pb_coadd_local_tree: more segments than the batch holds");
@@ -1304,6 +1337,7 @@ extern "C" int pb_coadd_local_tree(pb_handle *h, int nseg, const int32_t *ant_or
 extern "C" int pb_coadd_tree(pb_handle *h, const float *const *d_leaves, int n, float *d_dst, size_t nfloat)
 {
     if (!h || !d_leaves || !d_dst) return PB_EINVAL;
+    if (int rc = no_coherence(h, "pb_coadd_tree")) return rc;
     if (n < 1 || n > PB_COADD_MAX_LEAVES) return fail(h, PB_EINVAL, "pb_coadd_tree: 1..PB_COADD_MAX_LEAVES leaves");
     if (nfloat & 3) return fail(h, PB_EINVAL, "pb_coadd_tree: nfloat must be a multiple of 4");
     for (int i = 0; i < n; ++i) {
@@ -1330,6 +1364,7 @@ extern "C" int pb_coadd_tree(pb_handle *h, const float *const *d_leaves, int n, 
 extern "C" int pb_set_coadd_target(pb_handle *h, float *d_sum)
 {
     if (!h) return PB_EINVAL;
+    if (int rc = no_coherence(h, "pb_set_coadd_target")) return rc;
     if (d_sum && (h->A != 1 || !h->cfg.keep_ave || h->cfg.fft_backend != PB_FFT_LDS))
         return fail(h, PB_ESTATE, "pb_set_coadd_target needs nant=1, keep_ave=1 and the LDS back end");
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -1367,6 +1402,7 @@ static int coadd_slots(pb_handle *h)
 extern "C" int pb_coadd_finish(pb_handle *h, int nseg, const float *d_sum, int nant_total, uint8_t *codes_host)
 {
     if (!h || !d_sum || nant_total < 1) return PB_EINVAL;
+    if (int rc = no_coherence(h, "pb_coadd_finish")) return rc;
     if (nseg < 1 || nseg > h->S) return fail(h, PB_EINVAL, "pb_coadd_finish: nseg out of range");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t nb = (size_t)h->S * h->trim;
@@ -1392,6 +1428,7 @@ extern "C" int pb_coadd_finish(pb_handle *h, int nseg, const float *d_sum, int n
 extern "C" int pb_coadd_digitise(pb_handle *h, const float *d_sum, size_t nfloat, int nant_total, uint8_t *d_codes)
 {
     if (!h || !d_sum || !d_codes || nant_total < 1) return PB_EINVAL;
+    if (int rc = no_coherence(h, "pb_coadd_digitise")) return rc;
     if (h->cfg.npol != 1) return fail(h, PB_ESTATE, "pb_coadd_digitise: a flat plane range is a code range only with npol = 1");
     if (nfloat == 0 || (nfloat & 7)) return fail(h, PB_EINVAL, "pb_coadd_digitise: nfloat must be a positive multiple of 8");
     if (((uintptr_t)d_sum & 15) || ((uintptr_t)d_codes & 3)) return fail(h, PB_EINVAL, "pb_coadd_digitise: misaligned buffer");
@@ -1406,6 +1443,7 @@ extern "C" int pb_coadd_digitise(pb_handle *h, const float *d_sum, size_t nfloat
 extern "C" int pb_coadd_publish(pb_handle *h, const uint8_t *d_codes, size_t nbytes)
 {
     if (!h || !d_codes) return PB_EINVAL;
+    if (int rc = no_coherence(h, "pb_coadd_publish")) return rc;
     const size_t nb = (size_t)h->S * h->trim;
     if (nbytes == 0 || nbytes > nb) return fail(h, PB_EINVAL, "pb_coadd_publish: more bytes than a batch holds");
     HIPCHK(h, hipSetDevice(h->cfg.device));

@@ -83,7 +83,7 @@ struct pb_handle {
     float *d_stats;        // debug: [A][3][2][S*R*25] pow,kur,dag
     float *d_fraw, *d_fkur;      // hipFFT path: f32 voltages, same indexing as d_in
     float2 *d_Xraw, *d_Xkur;     // hipFFT path: [A][S][2][R][6251]
-    float *d_Praw, *d_Pkur;      // LDS path: power [A][S][2][R][4096]
+    float *d_Praw, *d_Pkur;      // LDS path: power [A][S][2][R][4096]; coherence: complex, float2 [A][S][2][R][4096]
     float *d_bp;           // [A][2 streams][2 pols][4096]
     uint8_t *d_codes;      // [A][2 streams][S][trim]
     float *d_ave;          // [A][2 streams][S][ave_per_seg]
@@ -157,6 +157,7 @@ hipError_t launch_dag_check(pb_handle *h, uint32_t bits_lo, uint64_t n, unsigned
 hipError_t launch_inject_c64(pb_handle *h, int nseg, int inject_now);
 hipError_t launch_detect(pb_handle *h, int nseg, int inject_now);
 hipError_t launch_detect_pow(pb_handle *h, int nseg);
+hipError_t launch_detect_coh(pb_handle *h, int nseg);   // coherence = 1 (k_detect_coh.hip)
 // device -> pinned host copy done by a kernel (see k_detect.hip: hipMemcpyAsync blocks the host now and then)
 hipError_t launch_copy_out(const PbSched &sched, uint8_t *host_pinned, const uint8_t *dev, size_t nbytes, hipStream_t st);
 hipError_t launch_channelize(pb_handle *h, int nseg, int inject_now);

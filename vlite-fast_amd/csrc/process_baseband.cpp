@@ -105,6 +105,7 @@ struct Args {
     unsigned key_in = 0x40, key_out = 0, key_co = 0;
     bool stdout_output = false, inject_frb = false, single_pass = false, profile_pass = false, no_control = false;
     bool dump_headers = false;
+    bool coherence = false;   // --coherence (with -P 2): AA, BB, CR, CI
     int write_fb = 2, nbit = 2, npol = 1, rfi_mode = 2, gpu_id = 0, taps = 1, rows_per_seg = 1024;
     int fft_backend = PB_FFT_LDS, control_port = MC_READER_PORT;
     std::vector<std::string> replay;
@@ -585,19 +586,19 @@ void usage()
     puts("usage: process_baseband -k <key_in hex> -K <key_out hex> -C <key_co hex> -w <0|1|2> -b <2|4|8> -P <1|2>\n"
          "       -r <0|1|2> -g <gpu> [-o] [-i] [-s] [-t] [-m] [-p N]\n"
          "       [--replay FILE...] [--out-sink FILE] [--co-sink FILE] [--datadir DIR] [--logdir DIR] [--no-control]\n"
-         "       [--fft-backend lds|hipfft] [--taps 1|4] [--rows-per-seg N] [--dump-headers]\n"
+         "       [--fft-backend lds|hipfft] [--taps 1|4] [--rows-per-seg N] [--dump-headers] [--coherence]\n"
          "       process_baseband --check-source NAME DATAID RA DEC");
 }
 
 bool parse(int argc, char **argv, Args &a)
 {
-    enum { O_REPLAY = 1000, O_DATADIR, O_LOGDIR, O_OUTSINK, O_COSINK, O_NOCTL, O_FFT, O_TAPS, O_ROWS, O_DUMP, O_CTLPORT };
+    enum { O_REPLAY = 1000, O_DATADIR, O_LOGDIR, O_OUTSINK, O_COSINK, O_NOCTL, O_FFT, O_TAPS, O_ROWS, O_DUMP, O_CTLPORT, O_COH };
     static option lo[] = {{"replay", required_argument, nullptr, O_REPLAY}, {"datadir", required_argument, nullptr, O_DATADIR},
                           {"logdir", required_argument, nullptr, O_LOGDIR},  {"out-sink", required_argument, nullptr, O_OUTSINK},
                           {"co-sink", required_argument, nullptr, O_COSINK}, {"no-control", no_argument, nullptr, O_NOCTL},
                           {"fft-backend", required_argument, nullptr, O_FFT}, {"taps", required_argument, nullptr, O_TAPS},
                           {"rows-per-seg", required_argument, nullptr, O_ROWS}, {"dump-headers", no_argument, nullptr, O_DUMP},
-                          {"control-port", required_argument, nullptr, O_CTLPORT},
+                          {"control-port", required_argument, nullptr, O_CTLPORT}, {"coherence", no_argument, nullptr, O_COH},
                           {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "hk:K:C:omiw:b:P:r:stg:p:", lo, nullptr)) != -1) {
@@ -635,12 +636,14 @@ bool parse(int argc, char **argv, Args &a)
         case O_ROWS: a.rows_per_seg = atoi(optarg); break;
         case O_DUMP: a.dump_headers = true; break;
         case O_CTLPORT: a.control_port = atoi(optarg); break;
+        case O_COH: a.coherence = true; break;
         default: return false;
         }
     }
     if (a.nbit != 2 && a.nbit != 4 && a.nbit != 8) { fputs("Unsupported NBIT!\n", stderr); return false; }
     if (a.rfi_mode < 0 || a.rfi_mode > 2) { fputs("Unsupported RFI mode!\n", stderr); return false; }
     if (a.npol != 1 && a.npol != 2) { fputs("Unsupported npol!\n", stderr); return false; }
+    if (a.coherence && a.npol != 2) { fputs("--coherence needs -P 2\n", stderr); return false; }
     if (a.rows_per_seg == 1024 && (a.gpu_id < 0 || a.gpu_id > 7)) { fputs("Unsupported GPU id!\n", stderr); return false; }
     return true;
 }
@@ -697,6 +700,7 @@ int run(const Args &args)
         cfg.max_seg = SEG_PER_SEC;
         cfg.inject_frb = args.inject_frb;
         cfg.nsets = nsets;
+        cfg.coherence = args.coherence ? 1 : 0;
         if (pb_create(&cfg, &h) != PB_OK) {
             log.line(true, "pb_create: %s", pb_last_error(nullptr));
             return 1;
@@ -759,10 +763,11 @@ int run(const Args &args)
         fb_names(t_unix, station, args.datadir, fb, fb_kur, cofb, cofb_kur);
         const std::string heimdall_file = args.rfi_mode ? fb_kur : fb, coheimdall_file = args.rfi_mode ? cofb_kur : cofb;
         const int64_t mjd = frame_mjd(vh), mjd_sec = frame_mjd_sec(vh);
+        const int out_npol = args.coherence ? 4 : args.npol;   // nifs / NPOL: AA, BB, CR, CI with --coherence
         const std::string sp_hdr = sigproc_header(station, atof(get(hdr, "RA", "0").c_str()), atof(get(hdr, "DEC", "0").c_str()),
-                                                  get(hdr, "NAME"), frame_dmjd(vh, (double)frames_per_sec), args.npol, args.nbit);
-        const std::string out_hdr = ascii_header_format(psrdada_out_header(hdr, args.npol, args.nbit, heimdall_file, t_unix, mjd, mjd_sec));
-        const std::string co_hdr = ascii_header_format(psrdada_out_header(hdr, args.npol, args.nbit, coheimdall_file, t_unix, mjd, mjd_sec));
+                                                  get(hdr, "NAME"), frame_dmjd(vh, (double)frames_per_sec), out_npol, args.nbit);
+        const std::string out_hdr = ascii_header_format(psrdada_out_header(hdr, out_npol, args.nbit, heimdall_file, t_unix, mjd, mjd_sec));
+        const std::string co_hdr = ascii_header_format(psrdada_out_header(hdr, out_npol, args.nbit, coheimdall_file, t_unix, mjd, mjd_sec));
         if (args.dump_headers) {
             hex("sigproc", sp_hdr);
             hex("out", out_hdr);

@@ -35,7 +35,7 @@ class PbConfig(C.Structure):
                 ("nbit", C.c_int32), ("npol", C.c_int32), ("rfi_mode", C.c_int32),
                 ("taps", C.c_int32), ("fft_backend", C.c_int32), ("rows_per_seg", C.c_int32),
                 ("max_seg", C.c_int32), ("inject_frb", C.c_int32), ("keep_ave", C.c_int32),
-                ("debug_keep", C.c_int32), ("nsets", C.c_int32)]
+                ("debug_keep", C.c_int32), ("nsets", C.c_int32), ("coherence", C.c_int32)]
 
 
 class PbSizes(C.Structure):
@@ -162,7 +162,7 @@ class PbHandle(object):
 
     def __init__(self, device=0, nant=1, nbit=8, npol=1, rfi_mode=2, taps=1, fft_backend=FFT_LDS,
                  rows_per_seg=1024, max_seg=10, inject_frb=False, keep_ave=False, debug_keep=False,
-                 nsets=1):
+                 nsets=1, coherence=False):
         L = load()
         cfg = PbConfig()
         L.pb_config_default(C.byref(cfg))
@@ -171,6 +171,7 @@ class PbHandle(object):
         cfg.rows_per_seg, cfg.max_seg = rows_per_seg, max_seg
         cfg.inject_frb, cfg.keep_ave, cfg.debug_keep = int(inject_frb), int(keep_ave), int(debug_keep)
         cfg.nsets = nsets
+        cfg.coherence = int(coherence)
         self._L = L
         self._h = C.c_void_p()
         rc = L.pb_create(C.byref(cfg), C.byref(self._h))

@@ -107,6 +107,8 @@ def build_parser():
     p.add_argument("--fft-backend", choices=["lds", "hipfft"], default="lds")
     p.add_argument("--taps", type=int, default=1)
     p.add_argument("--rows-per-seg", type=int, default=1024, help="test hook: shorter segments")
+    p.add_argument("--coherence", action="store_true",
+                   help="with -P 2: write AA, BB, CR, CI (nifs 4, NPOL 4) instead of AA, BB")
     return p
 
 
@@ -117,8 +119,15 @@ def validate(args):
         raise SystemExit("Unsupported RFI mode!")
     if args.npol not in (1, 2):
         raise SystemExit("Unsupported npol!")
+    if getattr(args, "coherence", False) and args.npol != 2:
+        raise SystemExit("--coherence needs -P 2")
     if args.rows_per_seg == 1024 and args.gpu_id not in (0, 1, 2, 3, 4, 5, 6, 7):
         raise SystemExit("Unsupported GPU id!")
+
+
+def out_npol(args):
+    """nifs / NPOL of the output: the -P value, 4 with --coherence (AA, BB, CR, CI)"""
+    return 4 if getattr(args, "coherence", False) else args.npol
 
 
 class Log(object):
@@ -296,7 +305,8 @@ def run(args, in_ring=None, out_ring=None, co_ring=None, handle=None, control_so
     if handle is None:
         handle = lp.PbHandle(device=args.gpu_id, nant=1, nbit=args.nbit, npol=args.npol, rfi_mode=args.rfi_mode,
                              taps=args.taps, fft_backend=lp.FFT_LDS if args.fft_backend == "lds" else lp.FFT_HIPFFT,
-                             rows_per_seg=R, max_seg=SEG_PER_SEC, inject_frb=args.inject_frb, nsets=2)
+                             rows_per_seg=R, max_seg=SEG_PER_SEC, inject_frb=args.inject_frb, nsets=2,
+                             coherence=getattr(args, "coherence", False))
     trim = handle.trim
     nsets = handle.nsets
     ctl = control_sock if control_sock is not None else (None if args.no_control else open_control_socket())
@@ -359,12 +369,13 @@ def run(args, in_ring=None, out_ring=None, co_ring=None, handle=None, control_so
         mjd, mjd_sec = vdif.frame_mjd(vh), vdif.frame_mjd_sec(vh)
         if out_ring is not None:
             out_ring.write_header(vdif.ascii_header_format(sigproc.psrdada_out_header(
-                hdr, vh, args.npol, args.nbit, heimdall_file, t_unix, mjd, mjd_sec)))
+                hdr, vh, out_npol(args), args.nbit, heimdall_file, t_unix, mjd, mjd_sec)))
         if co_ring is not None:
             co_ring.write_header(vdif.ascii_header_format(sigproc.psrdada_out_header(
-                hdr, vh, args.npol, args.nbit, coheimdall_file, t_unix, mjd, mjd_sec)))
+                hdr, vh, out_npol(args), args.nbit, coheimdall_file, t_unix, mjd, mjd_sec)))
         sp_hdr = sigproc.sigproc_header(station, float(hdr.get("RA", 0)), float(hdr.get("DEC", 0)),
-                                        hdr.get("NAME", ""), vdif.frame_dmjd(vh, frames_per_sec), args.npol, args.nbit)
+                                        hdr.get("NAME", ""), vdif.frame_dmjd(vh, frames_per_sec), out_npol(args),
+                                        args.nbit)
         fb_fp.write(sp_hdr)
         if fb_kur_fp:
             fb_kur_fp.write(sp_hdr)
