@@ -307,8 +307,37 @@ int pb_search_set_baseline(pb_search *s, int window_samples);
  * S/N (float bits), log2 width, at most max_out of them; *npeaks = how many there were. */
 int pb_search_peaks(pb_search *s, const void *codes, int codes_on_device, int nsamp, int nbit, float threshold,
                     int32_t *peaks, int max_out, int *npeaks, int *tout);
-/* device time of the last run's stages in ms: H2D, transpose, dedisperse, prefix + statistics, boxcar, D2H */
+/* device time of the last run's stages in ms: H2D, transpose, dedisperse, prefix + statistics, boxcar, D2H
+ * (a run with RFI cleaning: the cleaning is in none of the six, see pb_search_rfi_info) */
 int pb_search_timers(const pb_search *s, float *ms6);
+
+/* RFI cleaning before dedispersion, heimdall's narrow and broad stages (its flags -rfi_no_narrow, -rfi_no_broad,
+ * -rfi_tol).  heimdall's own algorithm is third-party and absent: what follows is THIS project's deterministic
+ * definition, and parity with heimdall's candidate list stays unpinned.  Off by default; when off nothing of it is
+ * launched and every output is what it is without this call.
+ * It runs on the channel-major u8 block xt[c][t] (after unpacking 8/4/2-bit codes), every sample t in [0, nsamp) of
+ * the block, the unzapped channels only, in place; dedispersion and everything after it read the cleaned codes.
+ *   narrow: per unzapped channel c, the 256-bin histogram of its nsamp codes; med_c = the smallest v whose cumulative
+ *           count is >= ceil(nsamp/2); mad_c = the smallest d for which #{x : |x - med_c| <= d} >= ceil(nsamp/2).
+ *           A sample is flagged when (float)|x - med_c| > tol * 1.4826f * (float)max(mad_c, 1) (binary32, left to
+ *           right, no contraction) and replaced by med_c.  At 2 bits |x - med_c| <= 3 < 3 * 1.4826, so nothing is
+ *           flagged with tol >= 3.
+ *   broad (after narrow): z[t] = exact sum of xt[c][t] over the unzapped channels; its level and rms by the formulas
+ *           of the per-DM statistics with the search's baseline window (pb_search_set_baseline); the boxcar S/N of
+ *           widths 2^0 .. rfi_boxcar_max as for a trial DM.  Each t0 whose best S/N is >= tol flags [t0, t0 + its
+ *           best width); every flagged t gets xt[c][t] = med_c in every unzapped channel (med_c of the narrow
+ *           definition; replacing outliers by the median leaves the median unchanged).
+ * Each block given to pb_search_run / pb_search_peaks is cleaned with its own statistics (heimdall cleans per gulp);
+ * a stream searched in overlapping gulps has the overlap cleaned again, with the next block's statistics.
+ * tol > 0 and finite (heimdall's -rfi_tol; 5 by default in search.py), rfi_boxcar_max a power of two in 1..64
+ * (16 by default), else PB_EINVAL with nothing changed.  narrow = broad = 0 switches cleaning off. */
+int pb_search_set_rfi(pb_search *s, int narrow, int broad, float tol, int rfi_boxcar_max);
+/* the last run's cleaning: samples flagged by the narrow pass (over all channels), time samples flagged by the broad
+ * pass, device time of the cleaning in ms (all 0 when the last run was not cleaned) */
+int pb_search_rfi_info(const pb_search *s, uint64_t *n_narrow, int *n_broad_samples, float *ms);
+/* the last run's channel-major block [nchan][nsamp] u8 after cleaning (zapped rows as transposed), for tests;
+ * nbytes >= nchan * nsamp */
+int pb_search_fetch_clean(pb_search *s, uint8_t *xt, size_t nbytes);
 
 /* Page-locked host memory for the blocks handed to pb_submit_vdif(_at) (H2D copies from pageable memory are
  * staged and synchronous); the reference allocates its 1-s host buffer the same way (cudaMallocHost,

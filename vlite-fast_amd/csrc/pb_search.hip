@@ -12,6 +12,10 @@
 //   3. per-DM mean / rms with one 3-sigma clip, boxcars 2^0..2^k (k = log2 boxcar_max):
 //      S/N(t, w) = (sum_{i<w} D[t+i] - w mean) / (rms sqrt(w)); keep the best width per (dm, t)
 // All integer up to the normalisation, so 1-2 are bit-exact vs the NumPy restatement.
+// Optional between 1 and 2: RFI cleaning of the channel-major block in place (pb_search_set_rfi; off by default, and
+// then nothing of it is launched).  The definition is include/pb_hip.h's; the kernels are k_rfi_narrow (per-channel
+// histogram, median, MAD, outliers -> median), then the zero-DM series through k_dedisperse / k_prefix /
+// k_series_stats / k_boxcar, k_rfi_broad_list (the flagged samples) and k_rfi_broad_mask (those samples -> median).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -43,6 +47,22 @@ struct pb_search {
     size_t tpitch;
     hipStream_t stream;
     std::string err;
+    // RFI cleaning (pb_search_set_rfi); the buffers exist once it has been switched on
+    int rfi_narrow, rfi_broad, rfi_nbox;
+    float rfi_tol;
+    int last_nsamp, rfi_ran;       // last run: block length, whether it was cleaned
+    int32_t *d_zdelay;             // [nact] zeros: k_dedisperse at DM 0 gives the zero-DM series
+    uint8_t *d_med;                // [nact] median code of each unzapped channel
+    uint32_t *d_z;                 // [tpitch] zero-DM series
+    uint64_t *d_zP;                // [tpitch + 8] its prefix sums
+    float *d_zstats, *d_zsnr;      // [2], [tpitch]
+    uint8_t *d_zwid;               // [tpitch]
+    int32_t *d_tlist;              // [tpitch] flagged samples of the broad pass
+    unsigned long long *d_rcnt;    // [2]: narrow flags, broad samples
+    hipEvent_t ev_rfi;             // end of cleaning (it starts at ev[2])
+    uint64_t n_narrow;
+    int n_broad;
+    float rfi_ms;
 };
 
 static std::string g_search_err;
@@ -333,6 +353,164 @@ __global__ __launch_bounds__(256) void k_boxcar(const uint64_t *__restrict__ P, 
     }
 }
 
+// ---- RFI cleaning (definition: include/pb_hip.h, pb_search_set_rfi) ----
+
+// Wave 0 of a workgroup, a[j] = count of bin 4 lane + j: the smallest bin whose cumulative count reaches `need`
+// (which the 256 bins together always reach), the same in every lane.
+__device__ __forceinline__ int first_bin_reaching(const uint32_t (&a)[4], uint32_t need)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t loc = a[0] + a[1] + a[2] + a[3];
+    uint32_t inc = loc;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(inc, o);
+        if (lane >= o) inc += y;
+    }
+    const int first = __builtin_ctzll(__ballot(inc >= need));
+    uint32_t c = inc - loc;
+    int k = 3;
+    for (int j = 0; j < 4; ++j) {
+        c += a[j];
+        if (c >= need) {
+            k = j;
+            break;
+        }
+    }
+    return __shfl(4 * lane + k, first);
+}
+
+// Narrow pass, one workgroup per unzapped channel: the row's 256-bin histogram (one per wave in LDS, then summed),
+// med = smallest v with cumulative count >= ceil(nsamp/2), mad = smallest d with #{|x - med| <= d} >= ceil(nsamp/2);
+// with `replace`, every x with (float)|x - med| > tol * 1.4826f * (float)max(mad, 1) becomes med (16-byte loads,
+// a 16-byte store only where a byte changed) and the flags are counted.  med goes to med_out for the broad pass.
+// The row is read twice from memory (it is at most max_samples bytes: the second read mostly hits the cache).
+__global__ __launch_bounds__(256) void k_rfi_narrow(uint8_t *__restrict__ xt, const int32_t *__restrict__ chans,
+                                                    uint8_t *__restrict__ med_out, int nsamp, size_t tpitch, float tol,
+                                                    int replace, unsigned long long *__restrict__ nflag)
+{
+    __shared__ uint32_t hist[4][256];
+    __shared__ uint32_t tot[256];
+    __shared__ int sh_med, sh_mad;
+    __shared__ uint32_t sh_cnt[4];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int i = threadIdx.x; i < 4 * 256; i += 256) hist[i >> 8][i & 255] = 0u;
+    __syncthreads();
+    uint8_t *row = xt + (size_t)chans[blockIdx.x] * tpitch;         // tpitch % 64 == 0: rows are 16-byte aligned
+    uint4 *rv = (uint4 *)row;
+    const int nvec = nsamp >> 4;
+    for (int i = threadIdx.x; i < nvec; i += 256) {
+        const uint4 v = rv[i];
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) atomicAdd(&hist[wave][(w[j] >> (8 * b)) & 255u], 1u);
+    }
+    for (int t = 16 * nvec + threadIdx.x; t < nsamp; t += 256) atomicAdd(&hist[wave][row[t]], 1u);
+    __syncthreads();
+    tot[threadIdx.x] = hist[0][threadIdx.x] + hist[1][threadIdx.x] + hist[2][threadIdx.x] + hist[3][threadIdx.x];
+    __syncthreads();
+    if (wave == 0) {
+        const uint32_t need = (uint32_t)(nsamp + 1) / 2;
+        uint32_t a[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a[j] = tot[4 * lane + j];
+        const int med = first_bin_reaching(a, need);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int d = 4 * lane + j;                             // count of |x - med| == d
+            a[j] = d == 0 ? tot[med] : (med - d >= 0 ? tot[med - d] : 0u) + (med + d < 256 ? tot[med + d] : 0u);
+        }
+        const int mad = first_bin_reaching(a, need);
+        if (lane == 0) {
+            sh_med = med;
+            sh_mad = mad;
+            med_out[blockIdx.x] = (uint8_t)med;
+        }
+    }
+    __syncthreads();
+    if (!replace) return;
+    const int med = sh_med;
+    // (float)d > thr for an integer d in 0..255 (exact in binary32) <=> d > dlim
+    const float thr = tol * 1.4826f * (float)max(sh_mad, 1);
+    const int dlim = thr >= 255.f ? 255 : (int)floorf(thr);
+    const uint32_t mb = (uint32_t)med;
+    uint32_t cnt = 0;
+    for (int i = threadIdx.x; i < nvec; i += 256) {
+        const uint4 v = rv[i];
+        uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        uint32_t changed = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            uint32_t o = 0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const uint32_t x = (w[j] >> (8 * b)) & 255u;
+                const bool f = abs((int)x - med) > dlim;
+                cnt += f;
+                changed |= f;
+                o |= (f ? mb : x) << (8 * b);
+            }
+            w[j] = o;
+        }
+        if (changed) rv[i] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    for (int t = 16 * nvec + threadIdx.x; t < nsamp; t += 256) {
+        if (abs((int)row[t] - med) > dlim) {
+            row[t] = (uint8_t)med;
+            ++cnt;
+        }
+    }
+    for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_down(cnt, o);
+    if (lane == 0) sh_cnt[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long n = (unsigned long long)sh_cnt[0] + sh_cnt[1] + sh_cnt[2] + sh_cnt[3];
+        if (n) atomicAdd(nflag, n);
+    }
+}
+
+// Broad pass, flagged samples: t is flagged when some t0 in [t - widest + 1, t] has best zero-DM S/N >= tol and
+// best width w with t0 + w > t.  Each flagged t is appended once to tlist (order unspecified), *nbroad counts them.
+// widest <= 64; the S/N / width of the 256 + 63 starts that can reach this workgroup's samples go through LDS.
+__global__ __launch_bounds__(256) void k_rfi_broad_list(const float *__restrict__ snr, const uint8_t *__restrict__ wid,
+                                                        int nsamp, float tol, int widest, int32_t *__restrict__ tlist,
+                                                        unsigned long long *__restrict__ nbroad)
+{
+    __shared__ int end[256 + 64];               // end[i]: t0 + w of start t0 = base - 64 + i if it is flagged, else 0
+    const int base = blockIdx.x * 256;
+    for (int i = threadIdx.x; i < 256 + 64; i += 256) {
+        const int t0 = base - 64 + i;
+        int e = 0;
+        if (t0 >= 0 && t0 < nsamp && snr[t0] >= tol) e = t0 + (1 << wid[t0]);
+        end[i] = e;
+    }
+    __syncthreads();
+    const int t = base + threadIdx.x;
+    if (t >= nsamp) return;
+    bool f = false;
+    for (int k = 0; k < widest; ++k) f |= end[64 + threadIdx.x - k] > t;
+    if (f) {
+        const unsigned long long i = atomicAdd(nbroad, 1ull);
+        tlist[i] = t;
+    }
+}
+
+// Broad pass, mask: every flagged sample of every unzapped channel becomes that channel's median; a wave per
+// channel, its lanes over the list.  Only the flagged samples are visited.
+__global__ __launch_bounds__(256) void k_rfi_broad_mask(uint8_t *__restrict__ xt, const int32_t *__restrict__ chans,
+                                                        const uint8_t *__restrict__ med, const int32_t *__restrict__ tlist,
+                                                        const unsigned long long *__restrict__ nbroad, int nact,
+                                                        size_t tpitch)
+{
+    const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (k >= nact) return;
+    const int n = (int)*nbroad;
+    uint8_t *row = xt + (size_t)chans[k] * tpitch;
+    const uint8_t m = med[k];
+    for (int i = threadIdx.x & 63; i < n; i += 64) row[tlist[i]] = m;
+}
+
 extern "C" const char *pb_search_last_error(const pb_search *s) { return s ? s->err.c_str() : g_search_err.c_str(); }
 
 static int search_create(int device, int nchan, int max_samples, float fch1_mhz, float foff_mhz, float tsamp_s,
@@ -416,6 +594,20 @@ static int search_create(int device, int nchan, int max_samples, float fch1_mhz,
     s->last_tout = 0;
     for (int i = 0; i < 6; ++i) s->ms[i] = 0.f;
     for (int i = 0; i < 7; ++i) s->ev[i] = nullptr;
+    s->rfi_narrow = s->rfi_broad = 0;
+    s->rfi_tol = 5.0f;
+    s->rfi_nbox = 5;
+    s->last_nsamp = s->rfi_ran = 0;
+    s->d_zdelay = s->d_tlist = nullptr;
+    s->d_med = s->d_zwid = nullptr;
+    s->d_z = nullptr;
+    s->d_zP = nullptr;
+    s->d_zstats = s->d_zsnr = nullptr;
+    s->d_rcnt = nullptr;
+    s->ev_rfi = nullptr;
+    s->n_narrow = 0;
+    s->n_broad = 0;
+    s->rfi_ms = 0.f;
     // delay table in double on the host; the top of the band (highest frequency) is the reference
     std::vector<int32_t> chans;
     for (int c = 0; c < nchan; ++c) {
@@ -476,9 +668,11 @@ extern "C" void pb_search_destroy(pb_search *s)
     if (!s) return;
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    void *p[] = {s->d_codes, s->d_xt, s->d_delay, s->d_D, s->d_stats, s->d_snr, s->d_wid, s->d_P, s->d_peaks, s->d_chans};
+    void *p[] = {s->d_codes, s->d_xt, s->d_delay, s->d_D, s->d_stats, s->d_snr, s->d_wid, s->d_P, s->d_peaks, s->d_chans,
+                 s->d_zdelay, s->d_med, s->d_z, s->d_zP, s->d_zstats, s->d_zsnr, s->d_zwid, s->d_tlist, s->d_rcnt};
     for (int i = 0; i < 7; ++i)
         if (s->ev[i]) (void)hipEventDestroy(s->ev[i]);
+    if (s->ev_rfi) (void)hipEventDestroy(s->ev_rfi);
     for (void *q : p)
         if (q) (void)hipFree(q);
     if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -498,6 +692,70 @@ extern "C" int pb_search_set_baseline(pb_search *s, int window_samples)
 {
     if (!s || window_samples < 0) return PB_EINVAL;
     s->baseline = window_samples;
+    return PB_OK;
+}
+
+extern "C" int pb_search_set_rfi(pb_search *s, int narrow, int broad, float tol, int rfi_boxcar_max)
+{
+    std::string &err = s ? s->err : g_search_err;
+    if (!(tol > 0) || !std::isfinite(tol)) {
+        err = "pb_search_set_rfi: tol must be > 0 and finite";
+        return PB_EINVAL;
+    }
+    if (rfi_boxcar_max < 1 || rfi_boxcar_max > 64 || (rfi_boxcar_max & (rfi_boxcar_max - 1))) {
+        err = "pb_search_set_rfi: rfi_boxcar_max must be a power of two in 1..64";
+        return PB_EINVAL;
+    }
+    if (!s) {
+        g_search_err = "pb_search_set_rfi: no search handle";
+        return PB_EINVAL;
+    }
+    if ((narrow || broad) && !s->d_rcnt) {
+        // the buffers of the cleaning, once: the zero-DM series has its own (the others are sized per trial DM)
+        const size_t tp = s->tpitch;
+        SCHK(s, hipSetDevice(s->device));
+        SCHK(s, hipMalloc((void **)&s->d_zdelay, (size_t)s->nact * sizeof(int32_t)));
+        SCHK(s, hipMemset(s->d_zdelay, 0, (size_t)s->nact * sizeof(int32_t)));
+        SCHK(s, hipMalloc((void **)&s->d_med, (size_t)s->nact));
+        SCHK(s, hipMalloc((void **)&s->d_z, tp * sizeof(uint32_t)));
+        SCHK(s, hipMalloc((void **)&s->d_zP, (tp + 8) * sizeof(uint64_t)));
+        SCHK(s, hipMalloc((void **)&s->d_zstats, 2 * sizeof(float)));
+        SCHK(s, hipMalloc((void **)&s->d_zsnr, tp * sizeof(float)));
+        SCHK(s, hipMalloc((void **)&s->d_zwid, tp));
+        SCHK(s, hipMalloc((void **)&s->d_tlist, tp * sizeof(int32_t)));
+        SCHK(s, hipEventCreate(&s->ev_rfi));
+        SCHK(s, hipMalloc((void **)&s->d_rcnt, 2 * sizeof(unsigned long long)));
+    }
+    s->rfi_narrow = narrow != 0;
+    s->rfi_broad = broad != 0;
+    s->rfi_tol = tol;
+    s->rfi_nbox = 0;
+    while ((1 << s->rfi_nbox) <= rfi_boxcar_max) s->rfi_nbox++;
+    return PB_OK;
+}
+
+// RFI cleaning of the transposed block in place (both parts or one), between ev[2] and ev_rfi
+static int search_clean(pb_search *s, int nsamp)
+{
+    const size_t ppitch = s->tpitch + 8;
+    SCHK(s, hipMemsetAsync(s->d_rcnt, 0, 2 * sizeof(unsigned long long), s->stream));
+    k_rfi_narrow<<<s->nact, 256, 0, s->stream>>>(s->d_xt, s->d_chans, s->d_med, nsamp, s->tpitch, s->rfi_tol,
+                                                 s->rfi_narrow, s->d_rcnt);
+    if (s->rfi_broad) {
+        dim3 gz((nsamp + DDM_TILE - 1) / DDM_TILE, 1);
+        k_dedisperse<<<gz, 256, 0, s->stream>>>(s->d_xt, s->d_chans, s->d_zdelay, s->d_z, s->nact, 1, nsamp, s->tpitch,
+                                                s->tpitch);
+        k_prefix<<<1, 256, 0, s->stream>>>(s->d_z, s->d_zP, nsamp, s->tpitch, ppitch);
+        k_series_stats<<<1, 256, 0, s->stream>>>(s->d_z, s->d_zP, s->d_zstats, nsamp, s->baseline, s->tpitch, ppitch);
+        dim3 gb((nsamp + 255) / 256, 1);
+        k_boxcar<<<gb, 256, 0, s->stream>>>(s->d_zP, s->d_zstats, s->d_zsnr, s->d_zwid, nsamp, s->rfi_nbox, s->baseline,
+                                            s->tpitch, ppitch, 0.f, nullptr, 0);
+        k_rfi_broad_list<<<gb, 256, 0, s->stream>>>(s->d_zsnr, s->d_zwid, nsamp, s->rfi_tol, 1 << (s->rfi_nbox - 1),
+                                                    s->d_tlist, s->d_rcnt + 1);
+        k_rfi_broad_mask<<<(s->nact + 3) / 4, 256, 0, s->stream>>>(s->d_xt, s->d_chans, s->d_med, s->d_tlist,
+                                                                   s->d_rcnt + 1, s->nact, s->tpitch);
+    }
+    SCHK(s, hipEventRecord(s->ev_rfi, s->stream));
     return PB_OK;
 }
 
@@ -526,6 +784,11 @@ static int search_run(pb_search *s, const void *codes, int codes_on_device, int 
     dim3 gt((nsamp + 63) / 64, (s->nchan + 63) / 64);
     k_transpose_codes<<<gt, 256, 0, s->stream>>>(d_codes, s->d_xt, nsamp, s->nchan, nbit, s->tpitch);
     SCHK(s, hipEventRecord(s->ev[2], s->stream));
+    s->rfi_ran = s->rfi_narrow || s->rfi_broad;
+    if (s->rfi_ran) {
+        const int rc = search_clean(s, nsamp);
+        if (rc) return rc;
+    }
     dim3 gd((tout + 255) / 256, s->ndm);
     dim3 gdd((tout + DDM_TILE - 1) / DDM_TILE, (s->ndm + DDM_DB - 1) / DDM_DB);
     k_dedisperse<<<gdd, 256, 0, s->stream>>>(s->d_xt, s->d_chans, s->d_delay, s->d_D, s->nact, s->ndm, tout, s->tpitch, s->tpitch);
@@ -540,15 +803,31 @@ static int search_run(pb_search *s, const void *codes, int codes_on_device, int 
     SCHK(s, hipEventRecord(s->ev[5], s->stream));
     SCHK(s, hipGetLastError());
     s->last_tout = tout;
+    s->last_nsamp = nsamp;
     return PB_OK;
 }
 
-static void search_times(pb_search *s)
+// after the run's last event: stage times, and the cleaning's time and counts (the dedispersion stage starts where
+// the cleaning ends)
+static int search_times(pb_search *s)
 {
     for (int i = 0; i < 6; ++i) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, s->ev[i], s->ev[i + 1]) == hipSuccess) s->ms[i] = ms;
+        const hipEvent_t a = (i == 2 && s->rfi_ran) ? s->ev_rfi : s->ev[i];
+        if (hipEventElapsedTime(&ms, a, s->ev[i + 1]) == hipSuccess) s->ms[i] = ms;
     }
+    s->n_narrow = 0;
+    s->n_broad = 0;
+    s->rfi_ms = 0.f;
+    if (s->rfi_ran) {
+        unsigned long long c[2];
+        SCHK(s, hipMemcpy(c, s->d_rcnt, sizeof c, hipMemcpyDeviceToHost));
+        s->n_narrow = c[0];
+        s->n_broad = (int)c[1];
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, s->ev[2], s->ev_rfi) == hipSuccess) s->rfi_ms = ms;
+    }
+    return PB_OK;
 }
 
 // codes: nsamp x nchan samples of nbit bits in SIGPROC order (host, or device if codes_on_device).
@@ -567,7 +846,8 @@ extern "C" int pb_search_run(pb_search *s, const void *codes, int codes_on_devic
     if (stats) SCHK(s, hipMemcpy(stats, s->d_stats, (size_t)s->ndm * 2 * sizeof(float), hipMemcpyDeviceToHost));
     SCHK(s, hipEventRecord(s->ev[6], s->stream));
     SCHK(s, hipEventSynchronize(s->ev[6]));
-    search_times(s);
+    rc = search_times(s);
+    if (rc) return rc;
     if (tout_out) *tout_out = tout;
     return PB_OK;
 }
@@ -588,7 +868,8 @@ extern "C" int pb_search_peaks(pb_search *s, const void *codes, int codes_on_dev
     if (ncopy > 0) SCHK(s, hipMemcpy(peaks, s->d_peaks + 1, (size_t)ncopy * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
     SCHK(s, hipEventRecord(s->ev[6], s->stream));
     SCHK(s, hipEventSynchronize(s->ev[6]));
-    search_times(s);
+    rc = search_times(s);
+    if (rc) return rc;
     *npeaks = n;
     if (tout_out) *tout_out = s->last_tout;
     return PB_OK;
@@ -598,5 +879,28 @@ extern "C" int pb_search_timers(const pb_search *s, float *ms6)
 {
     if (!s || !ms6) return PB_EINVAL;
     for (int i = 0; i < 6; ++i) ms6[i] = s->ms[i];
+    return PB_OK;
+}
+
+extern "C" int pb_search_rfi_info(const pb_search *s, uint64_t *n_narrow, int *n_broad_samples, float *ms)
+{
+    if (!s) return PB_EINVAL;
+    if (n_narrow) *n_narrow = s->n_narrow;
+    if (n_broad_samples) *n_broad_samples = s->n_broad;
+    if (ms) *ms = s->rfi_ms;
+    return PB_OK;
+}
+
+extern "C" int pb_search_fetch_clean(pb_search *s, uint8_t *xt, size_t nbytes)
+{
+    if (!s || !xt) return PB_EINVAL;
+    const size_t n = s->last_nsamp;
+    if (n == 0 || nbytes < n * s->nchan) {
+        s->err = "pb_search_fetch_clean: no block searched yet, or the buffer is smaller than nchan x nsamp";
+        return PB_EINVAL;
+    }
+    SCHK(s, hipSetDevice(s->device));
+    SCHK(s, hipStreamSynchronize(s->stream));
+    SCHK(s, hipMemcpy2D(xt, n, s->d_xt, s->tpitch, n, s->nchan, hipMemcpyDeviceToHost));
     return PB_OK;
 }

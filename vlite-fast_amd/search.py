@@ -74,6 +74,7 @@ class Searcher(object):
         self.ndm, self.nbox, self.max_delay = ndm.value, nbox.value, md.value
         self.nchan, self.tsamp = nchan, tsamp
         self.dms = dm_min + dm_step * np.arange(self.ndm) if dm_list is None else np.asarray(dm_list, np.float64)
+        self._nsamp = 0
 
     def close(self):
         if getattr(self, "_s", None):
@@ -98,6 +99,27 @@ class Searcher(object):
         if rc != 0:
             raise ValueError("baseline window must be >= 0")
 
+    def set_rfi(self, narrow=True, broad=True, tol=5.0, boxcar_max=16):
+        """RFI cleaning of every following block before dedispersion (heimdall's narrow and broad stages, this
+        project's own definition: include/pb_hip.h, pb_search_set_rfi); set_rfi(False, False) switches it off"""
+        rc = self._L.pb_search_set_rfi(self._s, int(bool(narrow)), int(bool(broad)), float(tol), int(boxcar_max))
+        if rc != 0:
+            raise ValueError(self._L.pb_search_last_error(self._s).decode())
+
+    def rfi_info(self):
+        """the last run's cleaning: narrow flags, broad time samples, device ms (0 when it was not cleaned)"""
+        n, b, ms = C.c_uint64(), C.c_int(), C.c_float()
+        self._L.pb_search_rfi_info(self._s, C.byref(n), C.byref(b), C.byref(ms))
+        return dict(n_narrow=int(n.value), n_broad_samples=int(b.value), ms=float(ms.value))
+
+    def fetch_clean(self):
+        """the last run's channel-major block [nchan][nsamp] u8 as dedispersion read it (cleaned if cleaning was on)"""
+        out = np.empty((self.nchan, self._nsamp), np.uint8)
+        rc = self._L.pb_search_fetch_clean(self._s, out.ctypes.data_as(C.POINTER(C.c_uint8)), out.nbytes)
+        if rc != 0:
+            raise self._lp.PbError("pb_search_fetch_clean failed (%d): %s" % (rc, self._L.pb_search_last_error(self._s).decode()))
+        return out
+
     def timers(self):
         """device ms of the last run's stages"""
         t = (C.c_float * 6)()
@@ -120,6 +142,7 @@ class Searcher(object):
                                      buf.ctypes.data_as(C.POINTER(C.c_int32)), max_out, C.byref(n), C.byref(t))
         if rc != 0:
             raise self._lp.PbError("pb_search_peaks failed (%d): %s" % (rc, self._L.pb_search_last_error(self._s).decode()))
+        self._nsamp = nsamp
         k = min(n.value, max_out, 1 << 20)        # (the device list holds 2^20 points)
         b = buf[:k]
         return dict(dmi=b[:, 0].copy(), t=b[:, 1].copy(), snr=b[:, 2].copy().view(np.float32), width_log2=b[:, 3].astype(np.uint8),
@@ -144,6 +167,7 @@ class Searcher(object):
                                    stats.ctypes.data_as(C.POINTER(C.c_float)), C.byref(t))
         if rc != 0:
             raise self._lp.PbError("pb_search_run failed (%d): %s" % (rc, self._L.pb_search_last_error(self._s).decode()))
+        self._nsamp = nsamp
         return dict(snr=snr, width_log2=wid, stats=stats, series=series, tout=tout)
 
 
@@ -216,7 +240,9 @@ class GulpSearch(object):
     each output sample is produced exactly once, with all widths, and neither a pulse whose sweep straddles a gulp
     boundary nor a wide one that starts just before it is lost.  push() returns the candidates of the samples that
     became complete; finish() those of the stream's last widest - 1 samples (narrow widths only: there is no more
-    data); sample indices count from the start of the stream."""
+    data); sample indices count from the start of the stream.  With RFI cleaning on (Searcher.set_rfi) every block is
+    cleaned with its own statistics, as heimdall cleans per gulp: the carried-over tail is cleaned again inside the
+    next block."""
 
     def __init__(self, searcher, threshold=6.0, nbit=8, coincidencer=None, utc_start="1970-01-01-00:00:00", beam=1):
         self.s, self.threshold, self.nbit = searcher, threshold, nbit
@@ -275,13 +301,9 @@ def candidate_line(c):
     return importlib.import_module((__package__ or "vlite-fast_amd") + ".candidates").candidate_line(c)
 
 
-def main(argv=None):
-    """heimdall's place in the chain for a SIGPROC file: `python -m vlite-fast_amd.search -f obs_kur.fil
-    -dm 2 1000 -boxcar_max 64 -nsamps_gulp 30720 -zap_chans 0 190 -zap_chans 3900 4096 -coincidencer vlite-nrl:27555`
-    (the flags of scripts/start_heimdall_single_antenna:21).  Prints heimdall-format candidate lines per gulp
-    and, with -coincidencer, sends them there."""
+def arg_parser():
+    """the command line of main(): heimdall's flag names"""
     import argparse
-    sig = importlib.import_module(_pkg + ".sigproc")
     ap = argparse.ArgumentParser(prog="search", prefix_chars="-")
     ap.add_argument("-f", dest="fil", required=True)
     ap.add_argument("-dm", nargs=2, type=float, default=list(HEIMDALL_DM))
@@ -295,7 +317,21 @@ def main(argv=None):
     ap.add_argument("-beam", type=int, default=1)
     ap.add_argument("-coincidencer", default=None)
     ap.add_argument("-gpu_id", type=int, default=0)
-    a = ap.parse_args(argv)
+    ap.add_argument("-rfi_clean", action="store_true", help="clean each gulp of RFI before dedispersion (narrow + broad)")
+    ap.add_argument("-rfi_tol", type=float, default=5.0, help="with -rfi_clean: the cleaning's threshold")
+    ap.add_argument("-rfi_no_narrow", action="store_true", help="with -rfi_clean: no per-channel outlier pass")
+    ap.add_argument("-rfi_no_broad", action="store_true", help="with -rfi_clean: no zero-DM impulse pass")
+    return ap
+
+
+def main(argv=None):
+    """heimdall's place in the chain for a SIGPROC file: `python -m vlite-fast_amd.search -f obs_kur.fil
+    -dm 2 1000 -boxcar_max 64 -nsamps_gulp 30720 -zap_chans 0 190 -zap_chans 3900 4096 -rfi_clean
+    -coincidencer vlite-nrl:27555` (the flags of scripts/start_heimdall_single_antenna:21; that launch leaves heimdall's
+    RFI cleaning on, which here is -rfi_clean).  Prints heimdall-format candidate lines per gulp and, with
+    -coincidencer, sends them there."""
+    sig = importlib.import_module(_pkg + ".sigproc")
+    a = arg_parser().parse_args(argv)
     with open(a.fil, "rb") as f:
         hdr, off = sig.read_header(f.read(4096))
     if hdr["nbits"] != 8 or hdr.get("nifs", 1) != 1:
@@ -308,6 +344,8 @@ def main(argv=None):
                                                                        - hdr["fch1"] ** -2) / tsamp) + 64,
                  dm_list=dml, dm_min=a.dm[0], dm_max=a.dm[1], dm_step=a.dm_step or 2.0, **kw)
     s.set_baseline(int(a.baseline_length / tsamp))
+    if a.rfi_clean:
+        s.set_rfi(narrow=not a.rfi_no_narrow, broad=not a.rfi_no_broad, tol=a.rfi_tol)
     import time as _time
     utc = _time.strftime("%Y-%m-%d-%H:%M:%S", _time.gmtime(round((hdr.get("tstart", 40587.0) - 40587.0) * 86400.0)))
     g = GulpSearch(s, threshold=a.detect_thresh, coincidencer=a.coincidencer, utc_start=utc, beam=a.beam)
