@@ -339,6 +339,42 @@ int pb_search_rfi_info(const pb_search *s, uint64_t *n_narrow, int *n_broad_samp
  * nbytes >= nchan * nsamp */
 int pb_search_fetch_clean(pb_search *s, uint8_t *xt, size_t nbytes);
 
+/* Per-candidate cutouts of the LAST block given to pb_search_run / pb_search_peaks, taken from what is still on the
+ * device: the dedispersed frequency-time image of an event and its DM-time "bow tie".  heimdall writes no such images:
+ * the definition is THIS project's own, every value an exact integer.  Off until pb_search_set_cutouts; a pb_search on
+ * which it was never called allocates nothing more, launches nothing more and returns what it returns without it.
+ * Notation: nsamp samples in the block, tout = nsamp - max_delay; xt[c][t] the channel-major u8 block after unpacking
+ * and, if switched on, after RFI cleaning; delay[dm][c] the integer delays of the unzapped channels as the search uses
+ * them; D[dm][t] the dedispersed series (pb_search_run's `series`); nact the number of unzapped channels.
+ * Geometry: nsub frequency subbands (nchan % nsub == 0; subband s = channels [s nchan/nsub, (s+1) nchan/nsub), zapped
+ * channels in it contribute nothing), nt time bins (even), ndmrow DM rows (even).
+ * A request is (dmi, t_pk, tscr): trial-DM index in [0, ndm), peak sample in block coordinates in [0, tout), time-scrunch
+ * factor, a power of two in 1..64.  Bin j covers the block samples T(j) = [t_pk + (j - nt/2) tscr,
+ * t_pk + (j - nt/2 + 1) tscr): a boxcar that starts at t_pk starts at the left edge of bin nt/2.
+ *   ft[s][j]      = sum over the unzapped channels c of subband s and t in T(j) of xt[c][t + delay[dmi][c]], over the
+ *                   terms with 0 <= t + delay[dmi][c] < nsamp only (t itself may lie outside [0, tout); bytes of the
+ *                   buffer at or beyond nsamp, stale from earlier blocks, are never summed)
+ *   ft_hits[s][j] = the number of such terms
+ *   dt[k][j]      = sum over t in T(j) with 0 <= t < tout of D[dmi - ndmrow/2 + k][t]; 0 where that DM index is outside
+ *                   [0, ndm)
+ *   dt_hits[k][j] = the number of samples summed (0 for a row outside the grid)
+ * all u32 (4096 channels x 64 samples x 255 < 2^32).  Means are ft / ft_hits and dt / (dt_hits nact), left to the
+ * reader.  For a bin whose samples all lie in [0, tout): sum_s ft[s][j] == dt[ndmrow/2][j] and
+ * sum_s ft_hits[s][j] == nact tscr; dt at tscr 1 is a crop of `series`.
+ * pb_search_set_cutouts allocates the device and page-locked host buffers for up to max_cands requests per call;
+ * max_cands = 0 frees them and switches cutouts off.  PB_EINVAL with nothing changed for nchan % nsub != 0, odd or
+ * non-positive nt / ndmrow, nt * 64 > max_samples (or nt > 8192: the bins are kept in LDS), max_cands < 0, or buffers
+ * beyond 2 GiB. */
+int pb_search_set_cutouts(pb_search *s, int nsub, int nt, int ndmrow, int max_cands);
+/* cands3: n triples (dmi, t_pk, tscr).  Outputs (host, any may be NULL): ft, ft_hits [n][nsub][nt]; dt, dt_hits
+ * [n][ndmrow][nt].  Runs on the search's stream after the run it refers to; one device-to-host copy per call.
+ * PB_EINVAL before anything is launched or written when cutouts are off, no block has been searched yet, n > max_cands
+ * or a triple is out of range (message: pb_search_last_error). */
+int pb_search_cutouts(pb_search *s, const int32_t *cands3, int n, uint32_t *ft, uint32_t *ft_hits, uint32_t *dt,
+                      uint32_t *dt_hits);
+/* device time of the last pb_search_cutouts in ms: the two kernels; the kernels and the copy to the host */
+int pb_search_cutout_timers(const pb_search *s, float *ms2);
+
 /* Page-locked host memory for the blocks handed to pb_submit_vdif(_at) (H2D copies from pageable memory are
  * staged and synchronous); the reference allocates its 1-s host buffer the same way (cudaMallocHost,
  * src/process_baseband.cu:579).  A host program above this ABI needs no HIP headers.  NULL on failure. */

@@ -16,10 +16,13 @@
 // then nothing of it is launched).  The definition is include/pb_hip.h's; the kernels are k_rfi_narrow (per-channel
 // histogram, median, MAD, outliers -> median), then the zero-DM series through k_dedisperse / k_prefix /
 // k_series_stats / k_boxcar, k_rfi_broad_list (the flagged samples) and k_rfi_broad_mask (those samples -> median).
+// Optional after a run: per-candidate cutouts of the block and of the dedispersed series that are still on the device
+// (pb_search_set_cutouts / pb_search_cutouts; definition in include/pb_hip.h): k_cutout_ft, k_cutout_dt.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -63,6 +66,14 @@ struct pb_search {
     uint64_t n_narrow;
     int n_broad;
     float rfi_ms;
+    // cutouts (pb_search_set_cutouts); the buffers exist while it is switched on (cut_max > 0)
+    int cut_nsub, cut_nt, cut_ndmrow, cut_max;
+    int32_t *d_cut_req;            // [cut_max][3] requests: DM index, peak sample, time-scrunch factor
+    int32_t *d_cut_sub;            // [cut_nsub][2] each subband's run [first, last) of chans[]
+    uint32_t *d_cut;               // one call's ft, ft_hits [n][nsub][nt] and dt, dt_hits [n][ndmrow][nt], back to back
+    uint32_t *h_cut;               // page-locked: the same, then the requests
+    hipEvent_t ev_cut[3];          // start, kernels done, copy done
+    float cut_ms[2];               // last call: kernels, kernels + D2H copy
 };
 
 static std::string g_search_err;
@@ -511,6 +522,204 @@ __global__ __launch_bounds__(256) void k_rfi_broad_mask(uint8_t *__restrict__ xt
     for (int i = threadIdx.x & 63; i < n; i += 64) row[tlist[i]] = m;
 }
 
+// ---- per-candidate cutouts (definition: include/pb_hip.h, pb_search_set_cutouts) ----
+
+typedef uint32_t cut_u32x4 __attribute__((ext_vector_type(4), aligned(4)));      // 16 bytes at a 4-byte aligned address
+
+#ifndef CUT_CU
+#define CUT_CU 4          // channels whose loads are in flight together
+#endif
+
+// 16 consecutive bytes of one channel's span, already shifted into place and masked, onto the unit's accumulators.
+// TS = 1 / 2: a bin is 1 / 2 bytes; TS = 4: tscr >= 4, a bin is a whole number of dwords (v_sad_u8 sums a dword's bytes).
+template <int TS>
+__device__ __forceinline__ void cutout_add(uint32_t (&acc)[16 / TS], const uint32_t (&a)[4])
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (TS == 1) {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc[(4 * i + b) % (16 / TS)] += (a[i] >> (8 * b)) & 255u;
+        } else if (TS == 2) {
+            acc[(2 * i) % (16 / TS)] = __builtin_amdgcn_sad_u8(a[i] & 0xffffu, 0u, acc[(2 * i) % (16 / TS)]);
+            acc[(2 * i + 1) % (16 / TS)] = __builtin_amdgcn_sad_u8(a[i] >> 16, 0u, acc[(2 * i + 1) % (16 / TS)]);
+        } else {
+            acc[i % (16 / TS)] = __builtin_amdgcn_sad_u8(a[i], 0u, acc[i % (16 / TS)]);
+        }
+    }
+}
+
+// One workgroup's subband of one candidate.  The span of a channel is the nt * tscr bytes from xt[c][t0 + delay]; it is
+// cut into 16-byte units, P lanes (a power of two) side by side take a channel's units, 256 / P channels go in
+// parallel, and a lane keeps its unit's sums in registers over all the channels it visits.  Per (channel, unit) the
+// bytes are five aligned dwords (one 16-byte and one 4-byte load) shifted by v_alignbyte as in k_dedisperse; the valid
+// byte range [lo, hi) of the unit -- inside [0, nsamp) of the row and inside the span -- is computed per unit and only
+// a unit that is cut by it is masked.  A unit with no valid byte loads nothing.  A unit with one reads at most 19
+// bytes past nsamp - 1 (inside the row's pitch, the next row or the allocation's 64-byte pad) and, before the row, the
+// previous row -- or, in the very first row, nothing: those dwords are not loaded.
+template <int TS>
+__device__ __forceinline__ void cutout_ft_body(uint32_t *bins, const uint8_t *__restrict__ xt,
+                                               const int32_t *__restrict__ chans, const int32_t *__restrict__ dl,
+                                               int first, int last, int t0, int lsh, int nt, int nsamp, size_t tpitch)
+{
+    constexpr int NA = 16 / TS;
+    const int span = nt << lsh;
+    const int nu = (span + 15) >> 4;
+    int P = 256;
+    while ((P >> 1) >= nu) P >>= 1;
+    const int slots = 256 / P, slot = threadIdx.x / P, ul = threadIdx.x % P;
+    for (int u = ul; u < nu; u += P) {
+        const int b0 = u << 4;
+        uint32_t acc[NA];
+#pragma unroll
+        for (int i = 0; i < NA; ++i) acc[i] = 0u;
+        for (int k = first + slot; k < last; k += slots * CUT_CU) {
+            uint32_t w[CUT_CU][5];
+            int lo[CUT_CU], hi[CUT_CU];
+            unsigned sh[CUT_CU];
+#pragma unroll
+            for (int q = 0; q < CUT_CU; ++q) {
+                const int kk = k + q * slots;
+                lo[q] = hi[q] = 0;
+                sh[q] = 0u;
+#pragma unroll
+                for (int i = 0; i < 5; ++i) w[q][i] = 0u;
+                if (kk >= last) continue;
+                const int s0 = t0 + dl[kk] + b0;                        // block sample of the unit's first byte
+                const int l = max(0, -s0), h = min(16, min(nsamp - s0, span - b0));
+                if (h <= l) continue;
+                lo[q] = l;
+                hi[q] = h;
+                sh[q] = (unsigned)(s0 & 3);
+                const long long off = (long long)chans[kk] * (long long)tpitch + (long long)(s0 & ~3);
+                if (off >= 0) {
+                    const uint32_t *p = (const uint32_t *)(xt + off);
+                    const cut_u32x4 v = *(const cut_u32x4 *)p;
+                    w[q][0] = v.x;
+                    w[q][1] = v.y;
+                    w[q][2] = v.z;
+                    w[q][3] = v.w;
+                    w[q][4] = p[4];
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 5; ++i)
+                        if (off + 4 * i >= 0) w[q][i] = *(const uint32_t *)(xt + off + 4 * i);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < CUT_CU; ++q) {
+                uint32_t a[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) a[i] = __builtin_amdgcn_alignbyte(w[q][i + 1], w[q][i], sh[q]);
+                if (lo[q] > 0 || hi[q] < 16) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int li = min(max(lo[q] - 4 * i, 0), 4), hj = min(max(hi[q] - 4 * i, 0), 4);
+                        uint32_t m = 0u;
+                        if (hj > li) m = (hj == 4 ? 0xffffffffu : (1u << (8 * hj)) - 1u) & ~((1u << (8 * li)) - 1u);
+                        a[i] &= m;
+                    }
+                }
+                cutout_add<TS>(acc, a);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            const int b = b0 + i * (TS == 4 ? 4 : TS);                  // first span byte of accumulator i
+            if (b < span && acc[i]) atomicAdd(&bins[b >> lsh], acc[i]);
+        }
+    }
+}
+
+// Frequency-time cutouts: grid (subband, candidate).  req: [n][3] = DM index, peak sample, time-scrunch factor (checked
+// on the host); subrun: [nsub][2] the subband's run [first, last) of chans[]; ft, fth: [n][nsub][nt].  The sums of the
+// workgroup's lanes meet in nt LDS bins; the hit counts are arithmetic (the overlap of each bin, shifted by each
+// channel's delay, with [0, nsamp)).
+__global__ __launch_bounds__(256) void k_cutout_ft(const uint8_t *__restrict__ xt, const int32_t *__restrict__ chans,
+                                                   const int32_t *__restrict__ delay, const int32_t *__restrict__ req,
+                                                   const int32_t *__restrict__ subrun, uint32_t *__restrict__ ft,
+                                                   uint32_t *__restrict__ fth, int nact, int nsamp, int nt, size_t tpitch)
+{
+    extern __shared__ uint32_t cut_bins[];
+    const int sub = blockIdx.x, cand = blockIdx.y;
+    const int dmi = req[3 * cand], tpk = req[3 * cand + 1], tscr = req[3 * cand + 2];
+    const int lsh = 31 - __clz(tscr);
+    const int t0 = tpk - ((nt / 2) << lsh);
+    const int first = subrun[2 * sub], last = subrun[2 * sub + 1];
+    const int32_t *dl = delay + (size_t)dmi * nact;
+    for (int j = threadIdx.x; j < nt; j += 256) cut_bins[j] = 0u;
+    __syncthreads();
+    if (tscr == 1)
+        cutout_ft_body<1>(cut_bins, xt, chans, dl, first, last, t0, lsh, nt, nsamp, tpitch);
+    else if (tscr == 2)
+        cutout_ft_body<2>(cut_bins, xt, chans, dl, first, last, t0, lsh, nt, nsamp, tpitch);
+    else
+        cutout_ft_body<4>(cut_bins, xt, chans, dl, first, last, t0, lsh, nt, nsamp, tpitch);
+    __syncthreads();
+    const size_t o = ((size_t)cand * gridDim.x + sub) * nt;
+    for (int j = threadIdx.x; j < nt; j += 256) {
+        const int b = t0 + (j << lsh);
+        uint32_t n = 0u;
+        for (int k = first; k < last; ++k) {
+            const int s0 = b + dl[k];
+            n += (uint32_t)max(min(s0 + tscr, nsamp) - max(s0, 0), 0);
+        }
+        ft[o + j] = cut_bins[j];
+        fth[o + j] = n;
+    }
+}
+
+// DM-time cutouts: grid (DM row, candidate); dt, dth: [n][ndmrow][nt].  tscr >= 4: a lane reads four consecutive
+// samples of the row (one 16-byte load where all four are inside [0, tout)), tscr / 4 neighbouring lanes make a bin.
+__global__ __launch_bounds__(256) void k_cutout_dt(const uint32_t *__restrict__ D, const int32_t *__restrict__ req,
+                                                   uint32_t *__restrict__ dt, uint32_t *__restrict__ dth, int ndm,
+                                                   int tout, int nt, size_t dpitch)
+{
+    const int row = blockIdx.x, cand = blockIdx.y, ndmrow = gridDim.x;
+    const int dmi = req[3 * cand], tpk = req[3 * cand + 1], tscr = req[3 * cand + 2];
+    const int lsh = 31 - __clz(tscr);
+    const int t0 = tpk - ((nt / 2) << lsh);
+    const int dm = dmi - ndmrow / 2 + row;
+    const bool in = dm >= 0 && dm < ndm;
+    uint32_t *out = dt + ((size_t)cand * ndmrow + row) * nt;
+    uint32_t *outh = dth + ((size_t)cand * ndmrow + row) * nt;
+    for (int j = threadIdx.x; j < nt; j += 256) {
+        const int b = t0 + (j << lsh);
+        outh[j] = in ? (uint32_t)max(min(b + tscr, tout) - max(b, 0), 0) : 0u;
+        if (!in) out[j] = 0u;
+    }
+    if (!in) return;
+    const uint32_t *x = D + (size_t)dm * dpitch;
+    if (tscr < 4) {
+        for (int j = threadIdx.x; j < nt; j += 256) {
+            const int b = t0 + (j << lsh);
+            uint32_t s = 0u;
+            for (int e = 0; e < tscr; ++e)
+                if (b + e >= 0 && b + e < tout) s += x[b + e];
+            out[j] = s;
+        }
+        return;
+    }
+    const int g = tscr >> 2;                    // lanes per bin: 1..16, groups aligned inside a wave
+    const int nq = nt * g;
+    for (int base = 0; base < nq; base += 256) {
+        const int i = base + threadIdx.x;
+        uint32_t s = 0u;
+        if (i < nq) {
+            const int t = t0 + 4 * i;
+            if (t >= 0 && t + 4 <= tout) {
+                const cut_u32x4 v = *(const cut_u32x4 *)(x + t);
+                s = v.x + v.y + v.z + v.w;
+            } else {
+                for (int e = 0; e < 4; ++e)
+                    if (t + e >= 0 && t + e < tout) s += x[t + e];
+            }
+        }
+        for (int o = 1; o < g; o <<= 1) s += __shfl_xor(s, o);
+        if (i < nq && (i & (g - 1)) == 0) out[i >> (lsh - 2)] = s;
+    }
+}
+
 extern "C" const char *pb_search_last_error(const pb_search *s) { return s ? s->err.c_str() : g_search_err.c_str(); }
 
 static int search_create(int device, int nchan, int max_samples, float fch1_mhz, float foff_mhz, float tsamp_s,
@@ -608,6 +817,11 @@ static int search_create(int device, int nchan, int max_samples, float fch1_mhz,
     s->n_narrow = 0;
     s->n_broad = 0;
     s->rfi_ms = 0.f;
+    s->cut_nsub = s->cut_nt = s->cut_ndmrow = s->cut_max = 0;
+    s->d_cut_req = s->d_cut_sub = nullptr;
+    s->d_cut = s->h_cut = nullptr;
+    for (int i = 0; i < 3; ++i) s->ev_cut[i] = nullptr;
+    s->cut_ms[0] = s->cut_ms[1] = 0.f;
     // delay table in double on the host; the top of the band (highest frequency) is the reference
     std::vector<int32_t> chans;
     for (int c = 0; c < nchan; ++c) {
@@ -663,6 +877,21 @@ static int search_create(int device, int nchan, int max_samples, float fch1_mhz,
     return PB_OK;
 }
 
+static void cutouts_free(pb_search *s)
+{
+    if (s->d_cut_req) (void)hipFree(s->d_cut_req);
+    if (s->d_cut_sub) (void)hipFree(s->d_cut_sub);
+    if (s->d_cut) (void)hipFree(s->d_cut);
+    if (s->h_cut) (void)hipHostFree(s->h_cut);
+    for (int i = 0; i < 3; ++i) {
+        if (s->ev_cut[i]) (void)hipEventDestroy(s->ev_cut[i]);
+        s->ev_cut[i] = nullptr;
+    }
+    s->d_cut_req = s->d_cut_sub = nullptr;
+    s->d_cut = s->h_cut = nullptr;
+    s->cut_nsub = s->cut_nt = s->cut_ndmrow = s->cut_max = 0;
+}
+
 extern "C" void pb_search_destroy(pb_search *s)
 {
     if (!s) return;
@@ -673,6 +902,7 @@ extern "C" void pb_search_destroy(pb_search *s)
     for (int i = 0; i < 7; ++i)
         if (s->ev[i]) (void)hipEventDestroy(s->ev[i]);
     if (s->ev_rfi) (void)hipEventDestroy(s->ev_rfi);
+    cutouts_free(s);
     for (void *q : p)
         if (q) (void)hipFree(q);
     if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -902,5 +1132,129 @@ extern "C" int pb_search_fetch_clean(pb_search *s, uint8_t *xt, size_t nbytes)
     SCHK(s, hipSetDevice(s->device));
     SCHK(s, hipStreamSynchronize(s->stream));
     SCHK(s, hipMemcpy2D(xt, n, s->d_xt, s->tpitch, n, s->nchan, hipMemcpyDeviceToHost));
+    return PB_OK;
+}
+
+#define CUT_MAX_NT 8192          // the bins of a frequency-time cutout live in LDS (4 bytes each)
+
+extern "C" int pb_search_set_cutouts(pb_search *s, int nsub, int nt, int ndmrow, int max_cands)
+{
+    if (!s) {
+        g_search_err = "pb_search_set_cutouts: no search handle";
+        return PB_EINVAL;
+    }
+    if (max_cands < 0) {
+        s->err = "pb_search_set_cutouts: max_cands must be >= 0";
+        return PB_EINVAL;
+    }
+    if (max_cands > 0) {
+        if (nsub < 1 || s->nchan % nsub) {
+            s->err = "pb_search_set_cutouts: nsub must divide the number of channels";
+            return PB_EINVAL;
+        }
+        if (nt < 2 || (nt & 1) || ndmrow < 2 || (ndmrow & 1)) {
+            s->err = "pb_search_set_cutouts: nt and ndmrow must be positive and even";
+            return PB_EINVAL;
+        }
+        if ((long long)nt * 64 > (long long)s->max_samples || nt > CUT_MAX_NT) {
+            s->err = "pb_search_set_cutouts: nt * 64 must not exceed max_samples (and nt 8192)";
+            return PB_EINVAL;
+        }
+        if ((long long)max_cands * ((long long)nsub + ndmrow) * nt > (1ll << 28)) {
+            s->err = "pb_search_set_cutouts: max_cands cutouts of this geometry exceed 2 GiB";
+            return PB_EINVAL;
+        }
+    }
+    SCHK(s, hipSetDevice(s->device));
+    SCHK(s, hipStreamSynchronize(s->stream));
+    cutouts_free(s);
+    if (max_cands == 0) return PB_OK;
+    // zapped channels are left out of chans[], so a subband's channels are one run of it
+    std::vector<int32_t> chans(s->nact), run(2 * (size_t)nsub);
+    SCHK(s, hipMemcpy(chans.data(), s->d_chans, chans.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    const int per = s->nchan / nsub;
+    int k = 0;
+    for (int b = 0; b < nsub; ++b) {
+        run[2 * b] = k;
+        while (k < s->nact && chans[k] < (b + 1) * per) ++k;
+        run[2 * b + 1] = k;
+    }
+    const size_t nout = 2 * (size_t)max_cands * ((size_t)nsub + ndmrow) * nt;
+    hipError_t e = hipMalloc((void **)&s->d_cut_req, (size_t)max_cands * 3 * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_cut_sub, run.size() * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemcpy(s->d_cut_sub, run.data(), run.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_cut, nout * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipHostMalloc((void **)&s->h_cut, (nout + (size_t)max_cands * 3) * sizeof(uint32_t), hipHostMallocDefault);
+    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&s->ev_cut[i]);
+    if (e != hipSuccess) {
+        cutouts_free(s);
+        s->err = std::string("pb_search_set_cutouts: ") + hipGetErrorString(e);
+        return PB_EHIP;
+    }
+    s->cut_nsub = nsub;
+    s->cut_nt = nt;
+    s->cut_ndmrow = ndmrow;
+    s->cut_max = max_cands;
+    return PB_OK;
+}
+
+extern "C" int pb_search_cutouts(pb_search *s, const int32_t *cands3, int n, uint32_t *ft, uint32_t *ft_hits, uint32_t *dt,
+                                 uint32_t *dt_hits)
+{
+    if (!s) {
+        g_search_err = "pb_search_cutouts: no search handle";
+        return PB_EINVAL;
+    }
+    if (s->cut_max == 0) {
+        s->err = "pb_search_cutouts: cutouts are not switched on (pb_search_set_cutouts)";
+        return PB_EINVAL;
+    }
+    if (s->last_nsamp == 0) {
+        s->err = "pb_search_cutouts: no block searched yet";
+        return PB_EINVAL;
+    }
+    if (!cands3 || n < 0 || n > s->cut_max) {
+        s->err = "pb_search_cutouts: no request list, or more requests than max_cands";
+        return PB_EINVAL;
+    }
+    for (int i = 0; i < n; ++i) {
+        const int dmi = cands3[3 * i], t = cands3[3 * i + 1], ts = cands3[3 * i + 2];
+        if (dmi < 0 || dmi >= s->ndm || t < 0 || t >= s->last_tout || ts < 1 || ts > 64 || (ts & (ts - 1))) {
+            s->err = "pb_search_cutouts: request " + std::to_string(i) + " out of range (DM index in [0, ndm), peak sample in "
+                     "[0, tout) of the last run, tscr a power of two in 1..64)";
+            return PB_EINVAL;
+        }
+    }
+    if (n == 0) return PB_OK;
+    const int nsub = s->cut_nsub, nt = s->cut_nt, nrow = s->cut_ndmrow;
+    const size_t nf = (size_t)n * nsub * nt, nd = (size_t)n * nrow * nt, nout = 2 * (nf + nd);
+    uint32_t *d_ft = s->d_cut, *d_fth = d_ft + nf, *d_dt = d_fth + nf, *d_dth = d_dt + nd;
+    int32_t *h_req = (int32_t *)(s->h_cut + 2 * (size_t)s->cut_max * ((size_t)nsub + nrow) * nt);
+    SCHK(s, hipSetDevice(s->device));
+    for (int i = 0; i < 3 * n; ++i) h_req[i] = cands3[i];
+    SCHK(s, hipMemcpyAsync(s->d_cut_req, h_req, (size_t)n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
+    SCHK(s, hipEventRecord(s->ev_cut[0], s->stream));
+    k_cutout_ft<<<dim3(nsub, n), 256, (size_t)nt * sizeof(uint32_t), s->stream>>>(
+        s->d_xt, s->d_chans, s->d_delay, s->d_cut_req, s->d_cut_sub, d_ft, d_fth, s->nact, s->last_nsamp, nt, s->tpitch);
+    k_cutout_dt<<<dim3(nrow, n), 256, 0, s->stream>>>(s->d_D, s->d_cut_req, d_dt, d_dth, s->ndm, s->last_tout, nt, s->tpitch);
+    SCHK(s, hipEventRecord(s->ev_cut[1], s->stream));
+    SCHK(s, hipMemcpyAsync(s->h_cut, s->d_cut, nout * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    SCHK(s, hipEventRecord(s->ev_cut[2], s->stream));
+    SCHK(s, hipGetLastError());
+    SCHK(s, hipEventSynchronize(s->ev_cut[2]));
+    for (int i = 0; i < 2; ++i)
+        if (hipEventElapsedTime(&s->cut_ms[i], s->ev_cut[0], s->ev_cut[i + 1]) != hipSuccess) s->cut_ms[i] = 0.f;
+    if (ft) memcpy(ft, s->h_cut, nf * sizeof(uint32_t));
+    if (ft_hits) memcpy(ft_hits, s->h_cut + nf, nf * sizeof(uint32_t));
+    if (dt) memcpy(dt, s->h_cut + 2 * nf, nd * sizeof(uint32_t));
+    if (dt_hits) memcpy(dt_hits, s->h_cut + 2 * nf + nd, nd * sizeof(uint32_t));
+    return PB_OK;
+}
+
+extern "C" int pb_search_cutout_timers(const pb_search *s, float *ms2)
+{
+    if (!s || !ms2) return PB_EINVAL;
+    ms2[0] = s->cut_ms[0];
+    ms2[1] = s->cut_ms[1];
     return PB_OK;
 }

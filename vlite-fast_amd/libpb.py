@@ -55,7 +55,8 @@ EXPORTS = ["pb_config_default", "pb_create", "pb_destroy", "pb_last_error", "pb_
            "pb_output_dev", "pb_coadd_local", "pb_coadd_local_codes", "pb_coadd_local_tree", "pb_coadd_tree", "pb_coadd_tree_order", "pb_coadd_digitise", "pb_coadd_publish", "pb_set_coadd_target", "pb_coadd_release", "pb_set_coadd_stream", "pb_coadd_finish", "pb_coadd_fetch_ptr", "pb_profile", "pb_get_timers", "pb_host_alloc", "pb_host_free",
            "pb_debug_fetch", "pb_debug_dag_check", "pb_channelize_f32", "pb_version", "pb_search_create", "pb_search_create_list", "pb_search_destroy",
            "pb_search_last_error", "pb_search_info", "pb_search_run", "pb_search_set_baseline", "pb_search_peaks",
-           "pb_search_timers", "pb_search_set_rfi", "pb_search_rfi_info", "pb_search_fetch_clean"]
+           "pb_search_timers", "pb_search_set_rfi", "pb_search_rfi_info", "pb_search_fetch_clean", "pb_search_set_cutouts",
+           "pb_search_cutouts", "pb_search_cutout_timers"]
 
 _lib = None
 
@@ -143,6 +144,10 @@ def load():
     L.pb_search_set_rfi.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_int]
     L.pb_search_rfi_info.argtypes = [vp, C.POINTER(C.c_uint64), ip, fp]
     L.pb_search_fetch_clean.argtypes = [vp, u8p, C.c_size_t]
+    u32p = C.POINTER(C.c_uint32)
+    L.pb_search_set_cutouts.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.pb_search_cutouts.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, u32p, u32p, u32p, u32p]
+    L.pb_search_cutout_timers.argtypes = [vp, fp]
     for n in EXPORTS:
         f = getattr(L, n)
         if f.restype is C.c_int or n in ("pb_create", "pb_query", "pb_sync"):

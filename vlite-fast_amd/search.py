@@ -73,6 +73,8 @@ class Searcher(object):
         self._L.pb_search_info(self._s, C.byref(ndm), C.byref(nbox), C.byref(md))
         self.ndm, self.nbox, self.max_delay = ndm.value, nbox.value, md.value
         self.nchan, self.tsamp = nchan, tsamp
+        self.fch1, self.foff = fch1, foff
+        self._cut = None                 # (nsub, nt, ndmrow, max_cands) once set_cutouts has switched them on
         self.dms = dm_min + dm_step * np.arange(self.ndm) if dm_list is None else np.asarray(dm_list, np.float64)
         self._nsamp = 0
 
@@ -119,6 +121,45 @@ class Searcher(object):
         if rc != 0:
             raise self._lp.PbError("pb_search_fetch_clean failed (%d): %s" % (rc, self._L.pb_search_last_error(self._s).decode()))
         return out
+
+    def set_cutouts(self, nsub=64, nt=256, ndmrow=64, max_cands=32):
+        """per-candidate cutouts of the last block (include/pb_hip.h, pb_search_set_cutouts): nsub subbands, nt time
+        bins, ndmrow DM rows, up to max_cands requests per cutouts() call; max_cands=0 switches them off"""
+        rc = self._L.pb_search_set_cutouts(self._s, int(nsub), int(nt), int(ndmrow), int(max_cands))
+        if rc != 0:
+            raise ValueError(self._L.pb_search_last_error(self._s).decode())
+        self._cut = (int(nsub), int(nt), int(ndmrow), int(max_cands)) if max_cands else None
+
+    def cutouts(self, dmi, t, tscr):
+        """Cutouts of the last block searched, one per request (dmi, t, tscr: scalars or equally long sequences; t in
+        block coordinates, tscr a power of two in 1..64).  Returns dict(ft, ft_hits [n][nsub][nt] u32, dt, dt_hits
+        [n][ndmrow][nt] u32, dm_rows [n][ndmrow] the DM of each row (NaN outside the grid), sub_freqs [nsub] the centre
+        frequency of each subband in MHz).  Bin j covers the samples t + (j - nt/2) tscr .. + tscr."""
+        if self._cut is None:
+            raise self._lp.PbError("cutouts are not switched on: call set_cutouts() first")
+        nsub, nt, nrow, _ = self._cut
+        req = np.stack(np.broadcast_arrays(np.atleast_1d(dmi), np.atleast_1d(t), np.atleast_1d(tscr)), axis=1)
+        req = np.ascontiguousarray(req, np.int32)
+        n = req.shape[0]
+        out = dict(ft=np.zeros((n, nsub, nt), np.uint32), ft_hits=np.zeros((n, nsub, nt), np.uint32),
+                   dt=np.zeros((n, nrow, nt), np.uint32), dt_hits=np.zeros((n, nrow, nt), np.uint32))
+        u32p = C.POINTER(C.c_uint32)
+        rc = self._L.pb_search_cutouts(self._s, req.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                                       *[out[k].ctypes.data_as(u32p) for k in ("ft", "ft_hits", "dt", "dt_hits")])
+        if rc != 0:
+            raise self._lp.PbError("pb_search_cutouts failed (%d): %s" % (rc, self._L.pb_search_last_error(self._s).decode()))
+        rows = req[:, :1].astype(np.int64) - nrow // 2 + np.arange(nrow)[None, :]
+        ok = (rows >= 0) & (rows < self.ndm)
+        out["dm_rows"] = np.where(ok, np.asarray(self.dms, np.float64)[np.clip(rows, 0, self.ndm - 1)], np.nan)
+        per = self.nchan // nsub
+        out["sub_freqs"] = self.fch1 + self.foff * (np.arange(nsub) * per + (per - 1) / 2.0)
+        return out
+
+    def cutout_timers(self):
+        """device ms of the last cutouts() call: the kernels; the kernels and the copy to the host"""
+        t = (C.c_float * 2)()
+        self._L.pb_search_cutout_timers(self._s, t)
+        return dict(kernels=float(t[0]), with_copy=float(t[1]))
 
     def timers(self):
         """device ms of the last run's stages"""
@@ -242,10 +283,21 @@ class GulpSearch(object):
     became complete; finish() those of the stream's last widest - 1 samples (narrow widths only: there is no more
     data); sample indices count from the start of the stream.  With RFI cleaning on (Searcher.set_rfi) every block is
     cleaned with its own statistics, as heimdall cleans per gulp: the carried-over tail is cleaned again inside the
-    next block."""
+    next block.
+    cutouts=dict(thresh=..., max_per_gulp=...) (the searcher's set_cutouts() must be on): of each push()'s or
+    finish()'s candidates those at or above thresh, strongest first, at most max_per_gulp (and at most the searcher's
+    max_cands), get a "cutout" entry -- dict(ft, ft_hits, dt, dt_hits, dm_rows, sub_freqs, tscr) of Searcher.cutouts
+    with tscr = max(1, width / 2) -- cut from the block that is still on the device.  Nothing else changes."""
 
-    def __init__(self, searcher, threshold=6.0, nbit=8, coincidencer=None, utc_start="1970-01-01-00:00:00", beam=1):
+    def __init__(self, searcher, threshold=6.0, nbit=8, coincidencer=None, utc_start="1970-01-01-00:00:00", beam=1,
+                 cutouts=None):
         self.s, self.threshold, self.nbit = searcher, threshold, nbit
+        self.cut = None
+        if cutouts is not None:
+            if searcher._cut is None:
+                raise ValueError("GulpSearch(cutouts=...): call the searcher's set_cutouts() first")
+            self.cut = (float(cutouts.get("thresh", threshold)), min(int(cutouts.get("max_per_gulp", 32)), searcher._cut[3]))
+        self.last_first = 0              # stream index of the first sample of the latest push()'s / finish()'s batch
         self.tail = np.zeros((0, searcher.nchan), np.uint8)
         self.done = 0                    # output samples produced so far = stream index of the next block's first output
         self.ov = (1 << (searcher.nbox - 1)) - 1        # widest boxcar - 1
@@ -257,6 +309,21 @@ class GulpSearch(object):
             cmod = importlib.import_module(_pkg + ".candidates")
             host, port = cmod.parse_coincidencer(self.coincidencer)
             cmod.send_candidates(host, port, self.utc_start, self.beam, cands, first_sample=first, nsamps=nsamps)
+
+    def _cutouts(self, cands, sample0):
+        """attach cutouts to the strongest candidates (group_points returns them strongest first, ties broken);
+        sample0: stream index of the current block's first output sample"""
+        if self.cut is None:
+            return
+        thresh, most = self.cut
+        sel = [c for c in cands if c["snr"] >= thresh][:most]
+        if not sel:
+            return
+        tscr = [max(1, (1 << c["tfilt"]) // 2) for c in sel]
+        r = self.s.cutouts([c["dmi"] for c in sel], [c["peak_idx"] - sample0 for c in sel], tscr)
+        for i, c in enumerate(sel):
+            c["cutout"] = dict(ft=r["ft"][i], ft_hits=r["ft_hits"][i], dt=r["dt"][i], dt_hits=r["dt_hits"][i],
+                               dm_rows=r["dm_rows"][i], sub_freqs=r["sub_freqs"], tscr=tscr[i])
 
     @staticmethod
     def _subset(pk, sel):
@@ -276,7 +343,8 @@ class GulpSearch(object):
         full = pk["t"] < nout
         cands = candidates_from_peaks(self._subset(pk, full), self.s.dms, self.s.tsamp, sample0=self.done)
         self.pending = (self._subset(pk, ~full), self.done, pk["tout"])
-        first = self.done
+        first = self.last_first = self.done
+        self._cutouts(cands, first)
         self.done += nout
         keep = min(self.s.max_delay + self.ov, data.shape[0])
         self.tail = data[data.shape[0] - keep:].copy()
@@ -290,6 +358,8 @@ class GulpSearch(object):
         pk, sample0, tout = self.pending
         self.pending = None
         cands = candidates_from_peaks(pk, self.s.dms, self.s.tsamp, sample0=sample0)
+        self._cutouts(cands, sample0)              # the block of the last push() is still the searcher's current one
+        self.last_first = self.done
         self._send(cands, self.done, tout - (self.done - sample0))
         self.done = sample0 + tout
         return cands
@@ -321,17 +391,68 @@ def arg_parser():
     ap.add_argument("-rfi_tol", type=float, default=5.0, help="with -rfi_clean: the cleaning's threshold")
     ap.add_argument("-rfi_no_narrow", action="store_true", help="with -rfi_clean: no per-channel outlier pass")
     ap.add_argument("-rfi_no_broad", action="store_true", help="with -rfi_clean: no zero-DM impulse pass")
+    ap.add_argument("-output_dir", default=None, help="write each gulp's candidate lines to <UTC>_<beam>.cand there")
+    ap.add_argument("-cutouts", action="store_true", help="with -output_dir: a .cutouts.npz beside each .cand file")
+    ap.add_argument("-cutout_thresh", type=float, default=None, help="with -cutouts: lowest S/N cut out (default: -detect_thresh)")
+    ap.add_argument("-cutout_max", type=int, default=32, help="with -cutouts: most cutouts per gulp")
     return ap
+
+
+def parse_args(argv=None):
+    """arg_parser() plus the checks between flags"""
+    ap = arg_parser()
+    a = ap.parse_args(argv)
+    if a.cutouts and not a.output_dir:
+        ap.error("-cutouts needs -output_dir")
+    if a.cutout_max < 1:
+        ap.error("-cutout_max must be >= 1")
+    if a.cutout_thresh is None:
+        a.cutout_thresh = a.detect_thresh
+    return a
+
+
+CUTOUT_KEYS = ("ft", "ft_hits", "dt", "dt_hits", "dm_rows")
+
+
+def write_cutouts_npz(path, cands, tsamp):
+    """The cutouts of one gulp's candidates (those that carry one; the others are left out) as one .npz: ft, ft_hits
+    [n][nsub][nt], dt, dt_hits [n][ndmrow][nt], dm_rows [n][ndmrow], sub_freqs [nsub], and per cutout peak_idx, dm, snr,
+    tfilt, tscr; tsamp.  Returns how many were written (0: no file)."""
+    cc = [c for c in cands if "cutout" in c]
+    if not cc:
+        return 0
+    d = {k: np.stack([c["cutout"][k] for c in cc]) for k in CUTOUT_KEYS}
+    d["sub_freqs"] = np.asarray(cc[0]["cutout"]["sub_freqs"], np.float64)
+    d["peak_idx"] = np.array([c["peak_idx"] for c in cc], np.int64)
+    d["dm"] = np.array([c["dm"] for c in cc], np.float64)
+    d["snr"] = np.array([c["snr"] for c in cc], np.float32)
+    d["tfilt"] = np.array([c["tfilt"] for c in cc], np.int32)
+    d["tscr"] = np.array([c["cutout"]["tscr"] for c in cc], np.int32)
+    d["tsamp"] = np.float64(tsamp)
+    with open(path, "wb") as f:
+        np.savez(f, **d)
+    return len(cc)
+
+
+def gulp_stem(utc_start, first_sample, tsamp, beam):
+    """<UTC of the gulp's first sample>_<beam, two digits>: the name heimdall gives a gulp's candidate file, as far as
+    this project knows it (unpinned)"""
+    import calendar
+    import time as _time
+    t0 = calendar.timegm(_time.strptime(utc_start, "%Y-%m-%d-%H:%M:%S"))
+    return "%s_%02d" % (_time.strftime("%Y-%m-%d-%H:%M:%S", _time.gmtime(t0 + int(first_sample * tsamp))), beam)
 
 
 def main(argv=None):
     """heimdall's place in the chain for a SIGPROC file: `python -m vlite-fast_amd.search -f obs_kur.fil
     -dm 2 1000 -boxcar_max 64 -nsamps_gulp 30720 -zap_chans 0 190 -zap_chans 3900 4096 -rfi_clean
-    -coincidencer vlite-nrl:27555` (the flags of scripts/start_heimdall_single_antenna:21; that launch leaves heimdall's
-    RFI cleaning on, which here is -rfi_clean).  Prints heimdall-format candidate lines per gulp and, with
-    -coincidencer, sends them there."""
+    -output_dir /mnt/ssd/cands -cutouts -coincidencer vlite-nrl:27555` (the flags of
+    scripts/start_heimdall_single_antenna:21; that launch leaves heimdall's RFI cleaning on, which here is -rfi_clean).
+    Prints heimdall-format candidate lines per gulp and, with -coincidencer, sends them there; with -output_dir each
+    gulp that has candidates also gets a .cand file of the same lines, with -cutouts a .cutouts.npz beside it."""
+    import os
     sig = importlib.import_module(_pkg + ".sigproc")
-    a = arg_parser().parse_args(argv)
+    a = parse_args(argv)
     with open(a.fil, "rb") as f:
         hdr, off = sig.read_header(f.read(4096))
     if hdr["nbits"] != 8 or hdr.get("nifs", 1) != 1:
@@ -340,28 +461,47 @@ def main(argv=None):
     zap = tuple(tuple(z) for z in a.zap_chans) if a.zap_chans else ()
     dml = None if a.dm_step > 0 else dedisp_dm_list(a.dm[0], a.dm[1], tsamp, hdr["fch1"], hdr["foff"], nchan, a.dm_tol)
     kw = dict(device=a.gpu_id, nchan=nchan, fch1=hdr["fch1"], foff=hdr["foff"], tsamp=tsamp, boxcar_max=a.boxcar_max, zap=zap)
-    s = Searcher(max_samples=a.nsamps_gulp + int(4.148808e3 * a.dm[1] * abs((hdr["fch1"] + (nchan - 1) * hdr["foff"]) ** -2
-                                                                       - hdr["fch1"] ** -2) / tsamp) + 64,
-                 dm_list=dml, dm_min=a.dm[0], dm_max=a.dm[1], dm_step=a.dm_step or 2.0, **kw)
+    maxs = a.nsamps_gulp + int(4.148808e3 * a.dm[1] * abs((hdr["fch1"] + (nchan - 1) * hdr["foff"]) ** -2
+                                                         - hdr["fch1"] ** -2) / tsamp) + 64
+    s = Searcher(max_samples=maxs, dm_list=dml, dm_min=a.dm[0], dm_max=a.dm[1], dm_step=a.dm_step or 2.0, **kw)
     s.set_baseline(int(a.baseline_length / tsamp))
     if a.rfi_clean:
         s.set_rfi(narrow=not a.rfi_no_narrow, broad=not a.rfi_no_broad, tol=a.rfi_tol)
     import time as _time
     utc = _time.strftime("%Y-%m-%d-%H:%M:%S", _time.gmtime(round((hdr.get("tstart", 40587.0) - 40587.0) * 86400.0)))
-    g = GulpSearch(s, threshold=a.detect_thresh, coincidencer=a.coincidencer, utc_start=utc, beam=a.beam)
-    ntot = 0
+    cut = None
+    if a.cutouts:
+        # the default geometry; fewer time bins where the blocks are too short for 256 bins of 64 samples, fewer
+        # subbands where 64 does not divide the band
+        s.set_cutouts(nsub=64 if nchan % 64 == 0 else 1, nt=min(256, (maxs // 64) & ~1), max_cands=a.cutout_max)
+        cut = dict(thresh=a.cutout_thresh, max_per_gulp=a.cutout_max)
+    g = GulpSearch(s, threshold=a.detect_thresh, coincidencer=a.coincidencer, utc_start=utc, beam=a.beam, cutouts=cut)
+    if a.output_dir:
+        os.makedirs(a.output_dir, exist_ok=True)
+    ntot, stems = 0, set()
+
+    def emit(cands):
+        for c in cands:
+            print(candidate_line(c))
+        if a.output_dir and cands:
+            stem = gulp_stem(utc, g.last_first, tsamp, a.beam)
+            if stem in stems:                       # gulps shorter than a second: keep the names apart
+                stem = "%s.%d_%02d" % (stem[:-3], g.last_first, a.beam)
+            stems.add(stem)
+            with open(os.path.join(a.output_dir, stem + ".cand"), "w") as f:
+                f.write("".join(candidate_line(c) + "\n" for c in cands))
+            if a.cutouts:
+                write_cutouts_npz(os.path.join(a.output_dir, stem + ".cutouts.npz"), cands, tsamp)
+        return len(cands)
+
     with open(a.fil, "rb") as f:
         f.seek(off)
         while True:
             blk = np.frombuffer(f.read(a.nsamps_gulp * nchan), np.uint8)
             if blk.size < nchan:
                 break
-            for c in g.push(blk[:blk.size // nchan * nchan].reshape(-1, nchan)):
-                print(candidate_line(c))
-                ntot += 1
-    for c in g.finish():
-        print(candidate_line(c))
-        ntot += 1
+            ntot += emit(g.push(blk[:blk.size // nchan * nchan].reshape(-1, nchan)))
+    ntot += emit(g.finish())
     s.close()
     return ntot
 
