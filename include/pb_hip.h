@@ -296,13 +296,40 @@ void pb_search_destroy(pb_search *s);
 const char *pb_search_last_error(const pb_search *s);
 int pb_search_info(const pb_search *s, int *ndm, int *nbox, int *max_delay);
 /* outputs (host; any may be NULL): snr / width_log2 / series are [ndm][tout], tout = nsamp - max_delay;
- * stats is [ndm][2] = clipped mean and rms of each dedispersed series */
+ * stats is [ndm][2] = level and rms of each dedispersed series (defined under pb_search_set_baseline below) */
 int pb_search_run(pb_search *s, const void *codes, int codes_on_device, int nsamp, int nbit, float *snr,
                   uint8_t *width_log2, uint32_t *series, float *stats, int *tout);
 /* Running baseline: the mean over `window_samples` samples around each sample is removed from every
  * dedispersed series before it is normalised (heimdall smooths its baseline over 2 s); 0 (default) = one
  * clipped mean per series. */
 int pb_search_set_baseline(pb_search *s, int window_samples);
+/* The normalisation, operation by operation (THIS project's own definition; heimdall's is third-party and absent).
+ * For one series x[0 .. n) of exact integers (a trial DM's D[dm][.] with n = tout, or the zero-DM series z of the broad
+ * RFI pass with n = nsamp) and the baseline window W = window_samples:
+ *   prefix sums   P[0] = 0, P[t + 1] = P[t] + x[t], exact 64-bit integers.
+ *   baseline      W > 0: the window of sample t is [lo, hi) = [t - W/2, t - W/2 + W) (W/2 rounds down).  If lo < 0 the
+ *                 window is [0, min(W, n)); then, if hi > n, it is [max(0, n - W), n).  b(t) = (P[hi] - P[lo]) / (hi - lo),
+ *                 the quotient of the two integers in double, rounded to binary32.
+ *                 W = 0: one constant for the series, g = P[n] / n in double, rounded to binary32.
+ *   residuals     v(t) = x[t] - b(t) (W > 0) or x[t] - g (W = 0), in double from the binary32 value.
+ *   first pass    over all n samples: m1 = sum v / n, var1 = sum v^2 / n - m1^2, r1 = sqrt(max(var1, 0)).
+ *   second pass   over the samples with |v(t) - m1| <= 3 r1 (there are cn of them; r1 = 0 keeps every sample):
+ *                 m2 = sum v / cn, var2 = sum (v - m2)^2 / cn, rms = sqrt(var2 / 0.97330) -- a Gaussian clipped at
+ *                 3 sigma keeps 0.9733 of its variance.  One clip, no iteration.
+ *   stats[dm][0]  the level: m2 + g for W = 0 (the clipped mean of the series itself), m2 for W > 0 (what is left to
+ *                 subtract on top of the running baseline; near zero).  stats[dm][1] = rms.  Both rounded to binary32.
+ *   The sums are accumulated in double in an unspecified order; the values above are those of exact sums, which the
+ *   double sums of at most a few 10^4 terms reproduce far below a binary32 ulp.  Where the second pass keeps only
+ *   equal samples (a constant block; a blanked block with one glitch; W = 1) every v - m2 is 0 and rms is exactly 0.
+ *   S/N           of the boxcar of width w = 2^k (k = 0 .. log2 boxcar_max) starting at t, defined when t + w <= n:
+ *                 base = b(t + w/2) + level (W > 0: the baseline under the boxcar's middle sample) or level (W = 0);
+ *                 S/N(t, w) = ((P[t + w] - P[t]) - w base) / (rms sqrt(w)), evaluated in binary32 from the binary32
+ *                 level, rms and b (the integer sum is rounded to binary32 first).
+ *   planes        snr[dm][t] = the largest S/N(t, w) over the widths that fit, width_log2[dm][t] = its k; of equal
+ *                 S/N the narrower width wins.  When rms is not positive, snr = 0 at every t, and width_log2 is the
+ *                 smallest k whose numerator (P[t + w] - P[t]) - w base is positive, 0 if none is.
+ * tests/search_stats_ref.py restates this in exact / double arithmetic; tests/test_gpu_search_stats.py holds the
+ * kernels to it (level and rms to 1 binary32 ulp, the planes to the rounding of the binary32 operands). */
 /* The same search returning only the points at or above `threshold`: peaks[4 i ..] = DM index, sample,
  * S/N (float bits), log2 width, at most max_out of them; *npeaks = how many there were. */
 int pb_search_peaks(pb_search *s, const void *codes, int codes_on_device, int nsamp, int nbit, float threshold,
@@ -322,9 +349,9 @@ int pb_search_timers(const pb_search *s, float *ms6);
  *           A sample is flagged when (float)|x - med_c| > tol * 1.4826f * (float)max(mad_c, 1) (binary32, left to
  *           right, no contraction) and replaced by med_c.  At 2 bits |x - med_c| <= 3 < 3 * 1.4826, so nothing is
  *           flagged with tol >= 3.
- *   broad (after narrow): z[t] = exact sum of xt[c][t] over the unzapped channels; its level and rms by the formulas
- *           of the per-DM statistics with the search's baseline window (pb_search_set_baseline); the boxcar S/N of
- *           widths 2^0 .. rfi_boxcar_max as for a trial DM.  Each t0 whose best S/N is >= tol flags [t0, t0 + its
+ *   broad (after narrow): z[t] = exact sum of xt[c][t] over the unzapped channels; its level and rms by the
+ *           definition under pb_search_set_baseline (x = z, n = nsamp, W = the search's baseline window); the boxcar
+ *           S/N and best width of widths 2^0 .. rfi_boxcar_max by the same definition.  Each t0 whose best S/N is >= tol flags [t0, t0 + its
  *           best width); every flagged t gets xt[c][t] = med_c in every unzapped channel (med_c of the narrow
  *           definition; replacing outliers by the median leaves the median unchanged).
  * Each block given to pb_search_run / pb_search_peaks is cleaned with its own statistics (heimdall cleans per gulp);

@@ -414,11 +414,11 @@ DM_CONST = 4.148808e3          # src/candidate.py:33: dm_delay = 4.148808e3 * dm
 
 
 def search_delays(dms, fch1, foff, nchan, tsamp):
-    """[ndm][nchan] delays in samples relative to the first (highest) channel: the formula of src/candidate.py:33 per
-    channel, rounded half up (floor(x + 0.5): the delays are >= 0, where it equals analysis/loc_step0.py:62's
-    np.round except on exact halves)."""
+    """[ndm][nchan] delays in samples relative to the highest channel (the first of a descending band, foff < 0; the
+    last of an ascending one): the formula of src/candidate.py:33 per channel, rounded half up (floor(x + 0.5): the
+    delays are >= 0, where it equals analysis/loc_step0.py:62's np.round except on exact halves)."""
     f = fch1 + foff * np.arange(nchan)
-    return np.stack([np.floor(DM_CONST * dm * (f ** -2 - f[0] ** -2) / tsamp + 0.5).astype(int) for dm in dms])
+    return np.stack([np.floor(DM_CONST * dm * (f ** -2 - f.max() ** -2) / tsamp + 0.5).astype(int) for dm in dms])
 
 
 def dedisperse_series(codes, delays, zap):

@@ -1,6 +1,6 @@
 """RFI cleaning in the search (pb_search_set_rfi, Searcher.set_rfi, search -rfi_clean) on the GPU: the narrow pass
 bit-exact against the NumPy restatement (tests/search_rfi_ref.py), the broad pass's flagged samples against the
-restatement fed with the GPU's own zero-DM level and rms, broadband bursts gone from the candidates at the production
+restatement fed with the GPU's own zero-DM level and rms (themselves held to tests/search_stats_ref.py), broadband bursts gone from the candidates at the production
 geometry while a dispersed pulse survives, byte-identical outputs with cleaning off, and the CLI.  The definition is
 this project's own (include/pb_hip.h); parity with heimdall's cleaning is unpinned."""
 import importlib
@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import search_rfi_ref as R
+import search_stats_ref as S
 import synth
 
 pytestmark = pytest.mark.gpu
@@ -105,6 +106,12 @@ def test_broad_pass_flags_the_restated_samples(W, narrow, boxcar_max):
         info = s.rfi_info()
     z, (level, rms) = _gpu_zero_dm(np.ascontiguousarray(xa.T), nchan, zap, W)
     assert np.array_equal(z, R.zero_dm(xa, chans))
+    # that level and rms are the definition's (tests/search_stats_ref.py, under test_gpu_search_stats.py's tolerance:
+    # rms 1 binary32 ulp, level 1 ulp + the summation bound), so the flag set is tied to the reference end to end
+    lvl_ref, rms_ref, n_boundary = S.series_stats(z.astype(np.int64), W)
+    assert n_boundary == 0
+    assert abs(float(rms) - float(rms_ref)) <= float(np.spacing(rms_ref)), (rms, rms_ref)
+    assert abs(float(level) - float(lvl_ref)) <= S.level_tolerance(z.astype(np.int64), W, lvl_ref), (level, lvl_ref)
     nbox = boxcar_max.bit_length()
     best, bw = R.zero_dm_snr(z, level, rms, nbox, W)
     sure = R.broad_flags(best, bw, tol * (1 + 1e-4))

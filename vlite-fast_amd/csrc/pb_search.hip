@@ -282,7 +282,8 @@ __device__ __forceinline__ float baseline_at(const uint64_t *__restrict__ p, int
     return (float)((double)(p[hi] - p[lo]) / (double)(hi - lo));
 }
 
-// mean and rms of each DM series about its baseline, then once more over the samples within 3 rms
+// mean and rms of each DM series about its baseline, then once more over the samples within 3 rms (definition:
+// include/pb_hip.h, under pb_search_set_baseline)
 __global__ __launch_bounds__(256) void k_series_stats(const uint32_t *__restrict__ D, const uint64_t *__restrict__ P,
                                                       float *__restrict__ stats, int tout, int W, size_t dpitch,
                                                       size_t ppitch)
@@ -301,23 +302,30 @@ __global__ __launch_bounds__(256) void k_series_stats(const uint32_t *__restrict
     s2 = block_sum(s2, sh);
     double mean = s1 / tout, var = s2 / tout - mean * mean;
     double rms = sqrt(var > 0 ? var : 0);
-    double c1 = 0, c2 = 0, cn = 0;
+    const double mean1 = mean, rms1 = rms;
+    double c1 = 0, cn = 0;
     for (int t = threadIdx.x; t < tout; t += 256) {
         const double v = (double)x[t] - (double)baseline_at(p, t, W, tout, gmean0);
-        if (fabs(v - mean) <= 3 * rms) {
+        if (fabs(v - mean1) <= 3 * rms1) {
             c1 += v;
-            c2 += v * v;
             cn += 1;
         }
     }
     c1 = block_sum(c1, sh);
-    c2 = block_sum(c2, sh);
     cn = block_sum(cn, sh);
-    if (cn > 0) {
+    if (cn > 0) {                                   // (the same in every lane: the barriers below are uniform)
         mean = c1 / cn;
-        var = c2 / cn - mean * mean;
+        // The variance about the clipped mean, in a pass of its own: sum v^2 / cn - mean^2 cancels to a rounding error
+        // of either sign where the clip leaves a constant (a blanked block with one glitch), and a positive one made
+        // an rms of 1e-9 and S/N of 1e11 there.  Here every kept v equals the mean and the rms is exactly 0.
+        double d2 = 0;
+        for (int t = threadIdx.x; t < tout; t += 256) {
+            const double v = (double)x[t] - (double)baseline_at(p, t, W, tout, gmean0);
+            if (fabs(v - mean1) <= 3 * rms1) d2 += (v - mean) * (v - mean);
+        }
+        d2 = block_sum(d2, sh);
         // a Gaussian clipped at 3 sigma has 0.9733 of its variance left
-        rms = sqrt((var > 0 ? var : 0) / 0.97330);
+        rms = sqrt(d2 / cn / 0.97330);
     }
     if (threadIdx.x == 0) {
         // [0]: level to subtract on top of the running baseline (W > 0) or the clipped mean itself (W == 0)
