@@ -402,6 +402,58 @@ int pb_search_cutouts(pb_search *s, const int32_t *cands3, int n, uint32_t *ft, 
 /* device time of the last pb_search_cutouts in ms: the two kernels; the kernels and the copy to the host */
 int pb_search_cutout_timers(const pb_search *s, float *ms2);
 
+/* A candidate's DM, width and S/N refined on the device, from the LAST block given to pb_search_run / pb_search_peaks:
+ * what the reference does after a trigger (analysis/loc_step0.py: optimize_pulse, refine_dm with analysis/utils.py's
+ * tophat_smooth and qn), with the reference's own estimators, on fine trial DMs about the candidate.  Off until
+ * pb_search_set_refine; a pb_search on which it was never called allocates nothing more, launches nothing more and
+ * returns exactly what it returns without it.
+ * Geometry: nstep fine trial DMs per request (32 by default in search.py), half_window H samples (128: the reference's
+ * 0.2 s at 781.25 us), wmax (32; the width pass tries the nw = wmax / 2 odd widths 1, 3, .. wmax - 1; M = wmax / 2).
+ * A request is (t_pk, width; dm_lo, dm_step): peak sample in block coordinates in [0, tout), width in 1 .. wmax -- an
+ * even width becomes width + 1 before anything else, as tophat_smooth makes it, and that odd number is the `width` of
+ * everything below (refine_dm itself would still scale by the even one; it is only ever given odd widths) -- and two
+ * binary32 numbers.  Fine trial k = 0 .. nstep - 1 has DM (double)dm_lo + k * (double)dm_step and the delays the search
+ * itself would give that DM: the formula in double, floor(d + 0.5), the unzapped channels, the top of the band as the
+ * reference (one function makes both tables).  A trial whose DM is below 0 or above the grid's last trial DM is not
+ * evaluated: its sn_dm is NaN, its series 0, and it cannot win.
+ * Definition, T = tout of the last run, window [i0, i1) = [max(0, t_pk - H), min(T, t_pk + H)), n = i1 - i0:
+ *   q_k[t]          exact sum over the unzapped channels c of xt[c][t + delay_k[c]], t in [0, T) (xt as the search
+ *                   dedispersed it: cleaned if cleaning is on).
+ *   smooth(q, t, w) (sum of q over [t - h, t + h]) / (2 h + 1), h = min(w / 2, t, T - 1 - t) (w / 2 rounds down): the
+ *                   quotient of the integers in double.  tophat_smooth on the whole series, edge ramps included.
+ *   med(x)          the median; the mean of the two middle values for an even count.  An integer or a half-integer.
+ *   qn(x)           2.2219 x the 25th percentile of all N (N - 1) / 2 absolute pair differences, interpolated linearly as
+ *                   np.percentile does: with the differences ascending, d[r] + (f / 4) (d[r + 1] - d[r]) where
+ *                   N (N - 1) / 2 - 1 = 4 r + f, 0 <= f < 4.  A multiple of 1/4 (exact) times 2.2219 (one rounding).
+ *   DM pass (refine_dm):   sn_dm[k] = (max over t in [i0, i1) of smooth(q_k, t, width) - med(q_k[i0:i1]))
+ *                                     / (qn(q_k[i0:i1]) / sqrt(width)),   0 where that qn is 0 (THIS project's rule;
+ *                   the reference divides by zero).  kbest = the first k with the largest sn_dm among the evaluated
+ *                   trials; -1 (and NaN / -1 from the width pass) when no trial of the request was evaluated.
+ *   width pass (optimize_pulse) on q = q_kbest: the off-pulse samples q[i0 : i0 + n/4] joined with q[i0 + 3n/4 : i1]
+ *                   (both quotients round down) give med and qn.  For each odd w = 1, 3, .. wmax - 1 the plain w-sample
+ *                   mean centred on t, (sum of q over [t - w/2, t + w/2]) / w, over t in [i0 + w, i1 - w); its first
+ *                   maximum, at t*, gives opt_loc = t* - i0 and opt_sn = (mean - med) / qn * sqrt(w), 0 where qn is 0.
+ *   Order statistics and sums are exact; the S/N are evaluated in double as written (IEEE, no contraction).
+ *   status          0, or 1 when n < 4 wmax (a window clipped by the block's ends to less than that): nothing is
+ *                   computed for that request, sn_dm and opt_sn are NaN, kbest and opt_loc -1, its series 0.
+ * tests/search_refine_ref.py restates this in NumPy; tests/golden/reference_refine.npz holds what the reference's own
+ * functions return on seeded planes, and tests/test_search_refine_cpu.py ties the two together.
+ * pb_search_set_refine allocates the device and page-locked host buffers for up to max_cands requests per call;
+ * max_cands = 0 frees them and switches refinement off.  PB_EINVAL with nothing changed for nstep outside 1..4096, wmax
+ * odd or outside 2..64, half_window < 2 wmax, half_window + wmax / 2 > 1024 (the statistics hold a series in LDS),
+ * max_cands < 0 or buffers beyond 1 GiB. */
+int pb_search_set_refine(pb_search *s, int nstep, int half_window, int wmax, int max_cands);
+/* req_i2: n pairs (t_pk, width); req_f2: n pairs (dm_lo, dm_step).  Outputs (host, any may be NULL): status [n],
+ * sn_dm [n][nstep], kbest [n], opt_sn [n][nw], opt_loc [n][nw]; series (for tests) [n][nstep][2 (H + M)] u32 = q_k over
+ * [t_pk - H - M, t_pk + H + M), 0 outside [0, T).  Runs on the search's stream after the run it refers to; one
+ * device-to-host copy per call, through page-locked memory.  PB_EINVAL before anything is launched or written when
+ * refinement is off, no block has been searched yet, n > max_cands or a request is out of range (t_pk outside [0, tout),
+ * width outside 1..wmax, dm_lo or dm_step not finite; message: pb_search_last_error). */
+int pb_search_refine(pb_search *s, const int32_t *req_i2, const float *req_f2, int n, int32_t *status, double *sn_dm,
+                     int32_t *kbest, double *opt_sn, int32_t *opt_loc, uint32_t *series);
+/* device time of the last pb_search_refine in ms: the three kernels; the kernels and the copy to the host */
+int pb_search_refine_timers(const pb_search *s, float *ms2);
+
 /* Page-locked host memory for the blocks handed to pb_submit_vdif(_at) (H2D copies from pageable memory are
  * staged and synchronous); the reference allocates its 1-s host buffer the same way (cudaMallocHost,
  * src/process_baseband.cu:579).  A host program above this ABI needs no HIP headers.  NULL on failure. */

@@ -18,6 +18,9 @@
 // k_series_stats / k_boxcar, k_rfi_broad_list (the flagged samples) and k_rfi_broad_mask (those samples -> median).
 // Optional after a run: per-candidate cutouts of the block and of the dedispersed series that are still on the device
 // (pb_search_set_cutouts / pb_search_cutouts; definition in include/pb_hip.h): k_cutout_ft, k_cutout_dt.
+// Optional after a run: a candidate's DM, width and S/N refined on a fine DM grid with the reference's estimator
+// (analysis/loc_step0.py: refine_dm, optimize_pulse), from the block that is still on the device (pb_search_set_refine /
+// pb_search_refine; definition in include/pb_hip.h): k_refine_series, k_refine_dm, k_refine_width.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -74,7 +77,28 @@ struct pb_search {
     uint32_t *h_cut;               // page-locked: the same, then the requests
     hipEvent_t ev_cut[3];          // start, kernels done, copy done
     float cut_ms[2];               // last call: kernels, kernels + D2H copy
+    // refinement (pb_search_set_refine); the buffers exist while it is switched on (rf_max > 0)
+    double dm_last, ftop;          // the grid's last trial DM; the delays' reference frequency (top of the band, MHz)
+    int rf_nstep, rf_H, rf_wmax, rf_max;
+    double *d_rf_g;                // [nact] f^-2 - ftop^-2 of each unzapped channel (delay_chan_term)
+    int32_t *d_rf_reqi;            // [rf_max][4] requests: peak sample, odd width, status, 0
+    float *d_rf_reqf;              // [rf_max][2] dm_lo, dm_step
+    double *d_rf_out;              // one call's sn_dm [n][nstep], opt_sn [n][nw] (double), kbest [n], opt_loc [n][nw] (i32),
+                                   // then the fine series about each peak [n][nstep][2 (H + M)] (u32)
+    double *h_rf;                  // page-locked: the same, then the series, then the requests
+    hipEvent_t ev_rf[3];           // start, kernels done, copy done
+    float rf_ms[2];                // last call: kernels, kernels + D2H copy
 };
+
+// The dispersion delay of one channel in samples, in double: 4.148808e3 MHz^2 s (src/candidate.py:33) x DM x
+// (f^-2 - ftop^-2) / tsamp, rounded half up.  The ONE place it is written: the trial DMs' table (search_create, host) and
+// the fine trials of the refinement (k_refine_series, device) both come from here; IEEE double, no contraction.
+static __host__ __device__ inline double delay_chan_term(double f, double ftop) { return 1.0 / (f * f) - 1.0 / (ftop * ftop); }
+static __host__ __device__ inline int32_t delay_samples(double dm, double chan_term, double tsamp)
+{
+    const double d = 4.148808e3 * dm * chan_term / tsamp;
+    return (int32_t)floor(d + 0.5);
+}
 
 static std::string g_search_err;
 
@@ -728,6 +752,321 @@ __global__ __launch_bounds__(256) void k_cutout_dt(const uint32_t *__restrict__ 
     }
 }
 
+// ---- refinement of a candidate's DM, width and S/N (definition: include/pb_hip.h, pb_search_set_refine) ----
+
+#define RF_MAXL 2048      // samples of one fine series about a peak, 2 (H + M); the statistics hold it in LDS
+#define RF_CH 1024        // channels whose delays are in LDS together
+#define RF_CU 4           // channels whose loads are in flight together
+
+// fine trial k of a request: DM (double)dm_lo + k (double)dm_step; evaluated only inside [0, the grid's last DM]
+__device__ __forceinline__ bool refine_trial(const int32_t *__restrict__ reqi, const float *__restrict__ reqf, int cand,
+                                             int k, double dm_last, double &dm)
+{
+    dm = (double)reqf[2 * cand] + (double)k * (double)reqf[2 * cand + 1];
+    return reqi[4 * cand + 2] == 0 && dm >= 0.0 && dm <= dm_last;
+}
+
+// The fine series: grid (fine trial, request).  series[cand][k][j] = q_k[t_pk - HM + j] = the sum over the unzapped
+// channels of xt[c][t + delay_k[c]] for t in [0, tout), 0 outside (and all 0 for a trial or request that is not
+// evaluated).  A lane takes 8 consecutive samples as in k_dedisperse -- three aligned dwords shifted by v_alignbyte,
+// packed 16-bit sums widened before they can overflow -- P = ceil(L / 8) lanes side by side cover the series and the
+// 256 / P groups of them share the channels; the groups' sums meet in LDS.  The delays of RF_CH channels at a time are
+// made in LDS by the whole workgroup with delay_samples, the function the trial DMs' table is made with.
+// Reads: a lane with a sample in [0, tout) reads at most 11 bytes past t + delay <= tout - 1 + max_delay = nsamp - 1 (the
+// trial's DM is not above the grid's last, and the delay grows with the DM), as k_dedisperse does; what it reads for
+// its samples outside [0, tout) -- the previous row, the pad -- is never written out; a dword before the allocation
+// (first row, t < 0) is not loaded.  So no byte at or beyond nsamp is ever summed into an output.
+__global__ __launch_bounds__(256) void k_refine_series(const uint8_t *__restrict__ xt, const int32_t *__restrict__ chans,
+                                                       const double *__restrict__ gterm, const int32_t *__restrict__ reqi,
+                                                       const float *__restrict__ reqf, uint32_t *__restrict__ series,
+                                                       int nact, int tout, int L, int HM, double tsamp, double dm_last,
+                                                       size_t tpitch)
+{
+    __shared__ int32_t dl[RF_CH];
+    __shared__ uint32_t part[256 * 8];
+    const int k = blockIdx.x, cand = blockIdx.y;
+    uint32_t *out = series + ((size_t)cand * gridDim.x + k) * L;
+    double dm;
+    if (!refine_trial(reqi, reqf, cand, k, dm_last, dm)) {              // the same in every lane
+        for (int j = threadIdx.x; j < L; j += 256) out[j] = 0u;
+        return;
+    }
+    const int P = (L + 7) >> 3, G = 256 / P;                            // P <= 256: pb_search_set_refine
+    const int grp = threadIdx.x / P, ul = threadIdx.x % P;
+    const int t0 = reqi[4 * cand] - HM;
+    const int ts = t0 + 8 * ul;
+    const bool live = grp < G && ts < tout && ts + 8 > 0;
+    uint32_t lo[2] = {0u, 0u}, hi[2] = {0u, 0u}, acc[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = 0u;
+    auto flush = [&]() {
+#pragma unroll
+        for (int w = 0; w < 2; ++w) {
+            acc[4 * w + 0] += lo[w] & 0xffffu;
+            acc[4 * w + 1] += hi[w] & 0xffffu;
+            acc[4 * w + 2] += lo[w] >> 16;
+            acc[4 * w + 3] += hi[w] >> 16;
+            lo[w] = hi[w] = 0u;
+        }
+    };
+    for (int c0 = 0; c0 < nact; c0 += RF_CH) {
+        const int nc = min(RF_CH, nact - c0);
+        __syncthreads();
+        for (int i = threadIdx.x; i < nc; i += 256) dl[i] = delay_samples(dm, gterm[c0 + i], tsamp);
+        __syncthreads();
+        if (!live) continue;
+        int since = 0;
+        for (int i = grp; i < nc; i += G * RF_CU) {
+            uint32_t w[RF_CU][3];
+            unsigned sh[RF_CU];
+#pragma unroll
+            for (int q = 0; q < RF_CU; ++q) {
+                const int ii = i + q * G;
+                w[q][0] = w[q][1] = w[q][2] = 0u;
+                sh[q] = 0u;
+                if (ii >= nc) continue;
+                const int s0 = ts + dl[ii];                             // block sample of the lane's first byte
+                sh[q] = (unsigned)(s0 & 3);
+                const long long off = (long long)chans[c0 + ii] * (long long)tpitch + (long long)(s0 & ~3);
+                if (off >= 0) {
+                    const uint32_t *p = (const uint32_t *)(xt + off);
+                    w[q][0] = p[0];
+                    w[q][1] = p[1];
+                    w[q][2] = p[2];
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 3; ++e)
+                        if (off + 4 * e >= 0) w[q][e] = *(const uint32_t *)(xt + off + 4 * e);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < RF_CU; ++q) {
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const uint32_t a = __builtin_amdgcn_alignbyte(w[q][e + 1], w[q][e], sh[q]);
+                    lo[e] += a & 0x00ff00ffu;
+                    hi[e] += (a >> 8) & 0x00ff00ffu;
+                }
+            }
+            since += RF_CU;
+            if (since >= 240) {                                         // 16-bit sums: at most 257 channels of 255
+                flush();
+                since = 0;
+            }
+        }
+        flush();
+    }
+    if (grp < G) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) part[(grp * P + ul) * 8 + i] = acc[i];
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < L; j += 256) {
+        uint32_t v = 0u;
+        for (int g = 0; g < G; ++g) v += part[g * P * 8 + j];
+        const int t = t0 + j;
+        out[j] = (t >= 0 && t < tout) ? v : 0u;
+    }
+}
+
+__device__ __forceinline__ uint32_t block_sum_u32(uint32_t v, uint32_t *sh)
+{
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+__device__ __forceinline__ uint64_t block_max_u64(uint64_t v, uint64_t *sh)
+{
+    for (int o = 32; o >= 1; o >>= 1) {
+        const uint64_t y = (uint64_t)__shfl_down((unsigned long long)v, o);
+        v = y > v ? y : v;
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const uint64_t a = sh[0] > sh[1] ? sh[0] : sh[1], b = sh[2] > sh[3] ? sh[2] : sh[3];
+    return a > b ? a : b;
+}
+
+// a double as a u64 that orders the same way (no NaN); never 0
+__device__ __forceinline__ uint64_t ordered_key(double v)
+{
+    const uint64_t b = (uint64_t)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+// src[0 .. n) -> dst ascending, both in LDS: every element counts the elements that go before it
+__device__ __forceinline__ void refine_sort(const uint32_t *src, int n, uint32_t *dst)
+{
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const uint32_t v = src[i];
+        int r = 0;
+        for (int j = 0; j < n; ++j) {
+            const uint32_t u = src[j];
+            r += (u < v) || (u == v && j < i);
+        }
+        dst[r] = v;
+    }
+    __syncthreads();
+}
+
+// first index in (i, n) whose value exceeds s[i] + v, n if none (s ascending)
+__device__ __forceinline__ int refine_upper(const uint32_t *s, int n, int i, uint32_t v)
+{
+    const uint64_t lim = (uint64_t)s[i] + v;
+    int lo = i + 1, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((uint64_t)s[mid] <= lim) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// number of pairs i < j with s[j] - s[i] <= v (the same in every lane)
+__device__ __forceinline__ uint32_t refine_pairs_le(const uint32_t *s, int n, uint32_t v, uint32_t *sh)
+{
+    uint32_t c = 0;
+    for (int i = threadIdx.x; i < n; i += 256) c += (uint32_t)(refine_upper(s, n, i, v) - i - 1);
+    return block_sum_u32(c, sh);
+}
+
+// Qn of the ascending s[0 .. n), n >= 2: 2.2219 x the 25th percentile of the np = n (n - 1) / 2 absolute pair differences,
+// interpolated as np.percentile does -- position (np - 1) / 4 = r + f / 4, value d[r] + (f / 4) (d[r + 1] - d[r]), exact
+// in double for integers.  d[r] by bisection on the value over the count of pairs at or below it; d[r + 1] is d[r] when
+// more than r + 1 pairs are at or below d[r], else the smallest difference above it.  Uniform over the workgroup.
+__device__ __forceinline__ double refine_qn(const uint32_t *s, int n, uint32_t *sh, uint64_t *sh64)
+{
+    const uint32_t np = (uint32_t)n * (uint32_t)(n - 1) / 2u, r = (np - 1u) >> 2, f = (np - 1u) & 3u;
+    uint32_t lo = 0u, hi = s[n - 1] - s[0];
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (refine_pairs_le(s, n, mid, sh) >= r + 1u) hi = mid; else lo = mid + 1u;
+    }
+    uint32_t dhi = lo;
+    if (f && refine_pairs_le(s, n, lo, sh) < r + 2u) {
+        uint64_t best = 0;                                              // ~(smallest difference above lo)
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const int j = refine_upper(s, n, i, lo);
+            if (j < n) {
+                const uint64_t key = ~(uint64_t)(s[j] - s[i]);
+                best = key > best ? key : best;
+            }
+        }
+        dhi = (uint32_t)~block_max_u64(best, sh64);
+    }
+    return 2.2219 * ((double)lo + 0.25 * (double)f * ((double)dhi - (double)lo));
+}
+
+// The DM pass, one workgroup per (fine trial, request): the window of the fine series in LDS, its median and Qn from a
+// sorted copy, the largest top-hat smoothed value with tophat_smooth's edge ramps at the ends of the whole series.
+__global__ __launch_bounds__(256) void k_refine_dm(const uint32_t *__restrict__ series, const int32_t *__restrict__ reqi,
+                                                   const float *__restrict__ reqf, double *__restrict__ sn_dm, int tout,
+                                                   int H, int M, double dm_last)
+{
+    __shared__ uint32_t ext[RF_MAXL], srt[RF_MAXL];
+    __shared__ uint32_t sh[4];
+    __shared__ uint64_t sh64[4];
+    const int k = blockIdx.x, cand = blockIdx.y, L = 2 * (H + M);
+    double dm;
+    if (!refine_trial(reqi, reqf, cand, k, dm_last, dm)) {              // the same in every lane
+        if (threadIdx.x == 0) sn_dm[(size_t)cand * gridDim.x + k] = __longlong_as_double(0x7ff8000000000000ll);
+        return;
+    }
+    const int tpk = reqi[4 * cand], w = reqi[4 * cand + 1];
+    const int i0 = max(0, tpk - H), i1 = min(tout, tpk + H), n = i1 - i0, e0 = i0 - (tpk - H - M);
+    const uint32_t *q = series + ((size_t)cand * gridDim.x + k) * L;
+    for (int j = threadIdx.x; j < L; j += 256) ext[j] = q[j];
+    __syncthreads();
+    refine_sort(ext + e0, n, srt);
+    const uint32_t med2 = srt[(n - 1) >> 1] + srt[n >> 1];
+    const double qn = refine_qn(srt, n, sh, sh64);
+    uint64_t key = 0;                                                   // the values are >= 0: their bits order as they do
+    for (int a = threadIdx.x; a < n; a += 256) {
+        const int t = i0 + a, h = min(w >> 1, min(t, tout - 1 - t));    // h <= M: the terms are inside ext
+        uint64_t sum = 0;
+        for (int e = e0 + a - h; e <= e0 + a + h; ++e) sum += ext[e];
+        const uint64_t b = (uint64_t)__double_as_longlong((double)sum / (double)(2 * h + 1));
+        key = b > key ? b : key;
+    }
+    key = block_max_u64(key, sh64);
+    if (threadIdx.x == 0) {
+        const double mx = __longlong_as_double((long long)key), med = 0.5 * (double)med2;
+        sn_dm[(size_t)cand * gridDim.x + k] = qn > 0.0 ? (mx - med) / (qn / sqrt((double)w)) : 0.0;
+    }
+}
+
+// The width pass, one workgroup per request: kbest = the first maximum of the request's sn_dm (NaN never wins), then on
+// that trial's series the off-pulse median and Qn and, for each odd width, the first maximum of the running mean.
+__global__ __launch_bounds__(256) void k_refine_width(const uint32_t *__restrict__ series, const int32_t *__restrict__ reqi,
+                                                      const double *__restrict__ sn_dm, int32_t *__restrict__ kbest,
+                                                      double *__restrict__ opt_sn, int32_t *__restrict__ opt_loc, int tout,
+                                                      int H, int M, int nstep, int nw)
+{
+    __shared__ uint32_t ext[RF_MAXL], off[RF_MAXL], srt[RF_MAXL];
+    __shared__ uint32_t sh[4];
+    __shared__ uint64_t sh64[4];
+    const int cand = blockIdx.x, L = 2 * (H + M);
+    uint64_t vkey = 0;
+    if (reqi[4 * cand + 2] == 0) {
+        for (int k = threadIdx.x; k < nstep; k += 256) {
+            const double v = sn_dm[(size_t)cand * nstep + k];
+            if (v == v) {
+                const uint64_t o = ordered_key(v);
+                vkey = o > vkey ? o : vkey;
+            }
+        }
+    }
+    vkey = block_max_u64(vkey, sh64);
+    if (vkey == 0) {                                                    // nothing evaluated; the same in every lane
+        if (threadIdx.x == 0) kbest[cand] = -1;
+        for (int iw = threadIdx.x; iw < nw; iw += 256) {
+            opt_sn[(size_t)cand * nw + iw] = __longlong_as_double(0x7ff8000000000000ll);
+            opt_loc[(size_t)cand * nw + iw] = -1;
+        }
+        return;
+    }
+    uint64_t ikey = 0;
+    for (int k = threadIdx.x; k < nstep; k += 256) {
+        const double v = sn_dm[(size_t)cand * nstep + k];
+        if (v == v && ordered_key(v) == vkey) {
+            const uint64_t o = ~(uint64_t)k;
+            ikey = o > ikey ? o : ikey;
+        }
+    }
+    const int kb = (int)~block_max_u64(ikey, sh64);
+    if (threadIdx.x == 0) kbest[cand] = kb;
+    const int tpk = reqi[4 * cand];
+    const int i0 = max(0, tpk - H), i1 = min(tout, tpk + H), n = i1 - i0, e0 = i0 - (tpk - H - M);
+    const uint32_t *q = series + ((size_t)cand * nstep + kb) * L;
+    for (int j = threadIdx.x; j < L; j += 256) ext[j] = q[j];
+    __syncthreads();
+    const int n4 = n / 4, n34 = 3 * n / 4, noff = n4 + n - n34;          // int(0.25 n), int(0.75 n)
+    for (int j = threadIdx.x; j < noff; j += 256) off[j] = j < n4 ? ext[e0 + j] : ext[e0 + n34 + (j - n4)];
+    __syncthreads();
+    refine_sort(off, noff, srt);
+    const double med = 0.5 * (double)(srt[(noff - 1) >> 1] + srt[noff >> 1]);
+    const double qn = refine_qn(srt, noff, sh, sh64);
+    for (int iw = 0; iw < nw; ++iw) {
+        const int w = 2 * iw + 1;
+        uint64_t key = 0;                                               // (sum, first position) as one number
+        for (int a = w + threadIdx.x; a < n - w; a += 256) {
+            uint32_t sum = 0;                                           // below 2^32: pb_search_set_refine
+            for (int e = e0 + a - iw; e <= e0 + a + iw; ++e) sum += ext[e];
+            const uint64_t o = ((uint64_t)sum << 32) | (uint64_t)(0xffffffffu - (uint32_t)a);
+            key = o > key ? o : key;
+        }
+        key = block_max_u64(key, sh64);
+        if (threadIdx.x == 0) {
+            const double mean = (double)(uint32_t)(key >> 32) / (double)w;
+            opt_loc[(size_t)cand * nw + iw] = (int32_t)(0xffffffffu - (uint32_t)key);
+            opt_sn[(size_t)cand * nw + iw] = qn > 0.0 ? (mean - med) / qn * sqrt((double)w) : 0.0;
+        }
+    }
+}
+
 extern "C" const char *pb_search_last_error(const pb_search *s) { return s ? s->err.c_str() : g_search_err.c_str(); }
 
 static int search_create(int device, int nchan, int max_samples, float fch1_mhz, float foff_mhz, float tsamp_s,
@@ -830,6 +1169,13 @@ static int search_create(int device, int nchan, int max_samples, float fch1_mhz,
     s->d_cut = s->h_cut = nullptr;
     for (int i = 0; i < 3; ++i) s->ev_cut[i] = nullptr;
     s->cut_ms[0] = s->cut_ms[1] = 0.f;
+    s->dm_last = dms.back();
+    s->rf_nstep = s->rf_H = s->rf_wmax = s->rf_max = 0;
+    s->d_rf_g = s->d_rf_out = s->h_rf = nullptr;
+    s->d_rf_reqi = nullptr;
+    s->d_rf_reqf = nullptr;
+    for (int i = 0; i < 3; ++i) s->ev_rf[i] = nullptr;
+    s->rf_ms[0] = s->rf_ms[1] = 0.f;
     // delay table in double on the host; the top of the band (highest frequency) is the reference
     std::vector<int32_t> chans;
     for (int c = 0; c < nchan; ++c) {
@@ -846,13 +1192,13 @@ static int search_create(int device, int nchan, int max_samples, float fch1_mhz,
     }
     std::vector<int32_t> delay((size_t)s->ndm * s->nact);
     const double ftop = foff_mhz < 0 ? fch1_mhz : fch1_mhz + (nchan - 1) * foff_mhz;
+    s->ftop = ftop;
     int maxd = 0;
     for (int i = 0; i < s->ndm; ++i) {
         const double dm = dms[i];
         for (int k = 0; k < s->nact; ++k) {
             const double f = (double)fch1_mhz + (double)chans[k] * (double)foff_mhz;
-            const double d = 4.148808e3 * dm * (1.0 / (f * f) - 1.0 / (ftop * ftop)) / (double)tsamp_s;
-            const int32_t di = (int32_t)floor(d + 0.5);
+            const int32_t di = delay_samples(dm, delay_chan_term(f, ftop), (double)tsamp_s);
             delay[(size_t)i * s->nact + k] = di;
             if (di > maxd) maxd = di;
         }
@@ -900,6 +1246,23 @@ static void cutouts_free(pb_search *s)
     s->cut_nsub = s->cut_nt = s->cut_ndmrow = s->cut_max = 0;
 }
 
+static void refine_free(pb_search *s)
+{
+    if (s->d_rf_g) (void)hipFree(s->d_rf_g);
+    if (s->d_rf_reqi) (void)hipFree(s->d_rf_reqi);
+    if (s->d_rf_reqf) (void)hipFree(s->d_rf_reqf);
+    if (s->d_rf_out) (void)hipFree(s->d_rf_out);
+    if (s->h_rf) (void)hipHostFree(s->h_rf);
+    for (int i = 0; i < 3; ++i) {
+        if (s->ev_rf[i]) (void)hipEventDestroy(s->ev_rf[i]);
+        s->ev_rf[i] = nullptr;
+    }
+    s->d_rf_g = s->d_rf_out = s->h_rf = nullptr;
+    s->d_rf_reqi = nullptr;
+    s->d_rf_reqf = nullptr;
+    s->rf_nstep = s->rf_H = s->rf_wmax = s->rf_max = 0;
+}
+
 extern "C" void pb_search_destroy(pb_search *s)
 {
     if (!s) return;
@@ -911,6 +1274,7 @@ extern "C" void pb_search_destroy(pb_search *s)
         if (s->ev[i]) (void)hipEventDestroy(s->ev[i]);
     if (s->ev_rfi) (void)hipEventDestroy(s->ev_rfi);
     cutouts_free(s);
+    refine_free(s);
     for (void *q : p)
         if (q) (void)hipFree(q);
     if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -1264,5 +1628,154 @@ extern "C" int pb_search_cutout_timers(const pb_search *s, float *ms2)
     if (!s || !ms2) return PB_EINVAL;
     ms2[0] = s->cut_ms[0];
     ms2[1] = s->cut_ms[1];
+    return PB_OK;
+}
+
+extern "C" int pb_search_set_refine(pb_search *s, int nstep, int half_window, int wmax, int max_cands)
+{
+    if (!s) {
+        g_search_err = "pb_search_set_refine: no search handle";
+        return PB_EINVAL;
+    }
+    if (max_cands < 0) {
+        s->err = "pb_search_set_refine: max_cands must be >= 0";
+        return PB_EINVAL;
+    }
+    if (max_cands > 0) {
+        if (nstep < 1 || nstep > 4096) {
+            s->err = "pb_search_set_refine: nstep must be in 1..4096";
+            return PB_EINVAL;
+        }
+        if (wmax < 2 || wmax > 64 || (wmax & 1)) {
+            s->err = "pb_search_set_refine: wmax must be even and in 2..64";
+            return PB_EINVAL;
+        }
+        if (half_window < 2 * wmax || 2 * (half_window + wmax / 2) > RF_MAXL) {
+            s->err = "pb_search_set_refine: half_window must be at least 2 wmax (a full window holds 4 wmax samples) and "
+                     "half_window + wmax / 2 at most 1024";
+            return PB_EINVAL;
+        }
+        if ((long long)s->nact * 255 * wmax >= (1ll << 32)) {
+            s->err = "pb_search_set_refine: too many channels for 32-bit running sums";
+            return PB_EINVAL;
+        }
+        if ((long long)max_cands * nstep * 2 * (half_window + wmax / 2) > (1ll << 28)) {
+            s->err = "pb_search_set_refine: max_cands requests of this geometry exceed 1 GiB";
+            return PB_EINVAL;
+        }
+    }
+    SCHK(s, hipSetDevice(s->device));
+    SCHK(s, hipStreamSynchronize(s->stream));
+    refine_free(s);
+    if (max_cands == 0) return PB_OK;
+    std::vector<int32_t> chans(s->nact);
+    SCHK(s, hipMemcpy(chans.data(), s->d_chans, chans.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::vector<double> g(s->nact);
+    for (int k = 0; k < s->nact; ++k)
+        g[k] = delay_chan_term((double)s->fch1 + (double)chans[k] * (double)s->foff, s->ftop);
+    const size_t L = 2 * ((size_t)half_window + wmax / 2), nw = wmax / 2;
+    const size_t nd = (size_t)max_cands * (nstep + nw), ni = (size_t)max_cands * (1 + nw), ns = (size_t)max_cands * nstep * L;
+    hipError_t e = hipMalloc((void **)&s->d_rf_g, g.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(s->d_rf_g, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_rf_reqi, (size_t)max_cands * 4 * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_rf_reqf, (size_t)max_cands * 2 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_rf_out, nd * sizeof(double) + (ni + ns) * sizeof(int32_t));
+    if (e == hipSuccess)
+        e = hipHostMalloc((void **)&s->h_rf, nd * sizeof(double) + (ni + ns + (size_t)max_cands * 6) * sizeof(int32_t),
+                          hipHostMallocDefault);
+    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&s->ev_rf[i]);
+    if (e != hipSuccess) {
+        refine_free(s);
+        s->err = std::string("pb_search_set_refine: ") + hipGetErrorString(e);
+        return PB_EHIP;
+    }
+    s->rf_nstep = nstep;
+    s->rf_H = half_window;
+    s->rf_wmax = wmax;
+    s->rf_max = max_cands;
+    return PB_OK;
+}
+
+extern "C" int pb_search_refine(pb_search *s, const int32_t *req_i2, const float *req_f2, int n, int32_t *status,
+                                double *sn_dm, int32_t *kbest, double *opt_sn, int32_t *opt_loc, uint32_t *series)
+{
+    if (!s) {
+        g_search_err = "pb_search_refine: no search handle";
+        return PB_EINVAL;
+    }
+    if (s->rf_max == 0) {
+        s->err = "pb_search_refine: refinement is not switched on (pb_search_set_refine)";
+        return PB_EINVAL;
+    }
+    if (s->last_nsamp == 0) {
+        s->err = "pb_search_refine: no block searched yet";
+        return PB_EINVAL;
+    }
+    if (!req_i2 || !req_f2 || n < 0 || n > s->rf_max) {
+        s->err = "pb_search_refine: no request list, or more requests than max_cands";
+        return PB_EINVAL;
+    }
+    const int T = s->last_tout, H = s->rf_H, M = s->rf_wmax / 2, nstep = s->rf_nstep, nw = M;
+    for (int i = 0; i < n; ++i) {
+        const int t = req_i2[2 * i], w = req_i2[2 * i + 1];
+        if (t < 0 || t >= T || w < 1 || w > s->rf_wmax || !std::isfinite(req_f2[2 * i]) || !std::isfinite(req_f2[2 * i + 1])) {
+            s->err = "pb_search_refine: request " + std::to_string(i) + " out of range (peak sample in [0, tout) of the last "
+                     "run, width in 1..wmax, dm_lo and dm_step finite)";
+            return PB_EINVAL;
+        }
+    }
+    if (n == 0) return PB_OK;
+    const size_t L = 2 * ((size_t)H + M);
+    const size_t nd = (size_t)n * (nstep + nw), ni = (size_t)n * (1 + nw), ns = (size_t)n * nstep * L;
+    // one buffer, so one copy: the doubles, the integers, then the series (copied only when it is asked for)
+    double *d_sn = s->d_rf_out, *d_osn = d_sn + (size_t)n * nstep;
+    int32_t *d_kb = (int32_t *)(s->d_rf_out + nd), *d_loc = d_kb + n;
+    uint32_t *d_ser = (uint32_t *)(d_kb + ni);
+    const size_t maxw = (size_t)s->rf_max * (nstep + nw) * 2 + (size_t)s->rf_max * (1 + nw) + (size_t)s->rf_max * nstep * L;
+    int32_t *h_reqi = (int32_t *)s->h_rf + maxw;
+    float *h_reqf = (float *)(h_reqi + 4 * (size_t)s->rf_max);
+    std::vector<int32_t> st(n);
+    for (int i = 0; i < n; ++i) {
+        const int t = req_i2[2 * i], w = req_i2[2 * i + 1];
+        st[i] = std::min(T, t + H) - std::max(0, t - H) < 4 * s->rf_wmax ? 1 : 0;
+        h_reqi[4 * i] = t;
+        h_reqi[4 * i + 1] = w | 1;                                      // an even width becomes width + 1
+        h_reqi[4 * i + 2] = st[i];
+        h_reqi[4 * i + 3] = 0;
+        h_reqf[2 * i] = req_f2[2 * i];
+        h_reqf[2 * i + 1] = req_f2[2 * i + 1];
+    }
+    SCHK(s, hipSetDevice(s->device));
+    SCHK(s, hipMemcpyAsync(s->d_rf_reqi, h_reqi, (size_t)n * 4 * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
+    SCHK(s, hipMemcpyAsync(s->d_rf_reqf, h_reqf, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    SCHK(s, hipEventRecord(s->ev_rf[0], s->stream));
+    k_refine_series<<<dim3(nstep, n), 256, 0, s->stream>>>(s->d_xt, s->d_chans, s->d_rf_g, s->d_rf_reqi, s->d_rf_reqf, d_ser,
+                                                           s->nact, T, (int)L, H + M, (double)s->tsamp, s->dm_last, s->tpitch);
+    k_refine_dm<<<dim3(nstep, n), 256, 0, s->stream>>>(d_ser, s->d_rf_reqi, s->d_rf_reqf, d_sn, T, H, M, s->dm_last);
+    k_refine_width<<<n, 256, 0, s->stream>>>(d_ser, s->d_rf_reqi, d_sn, d_kb, d_osn, d_loc, T, H, M, nstep, nw);
+    SCHK(s, hipEventRecord(s->ev_rf[1], s->stream));
+    const size_t nbytes = nd * sizeof(double) + (ni + (series ? ns : 0)) * sizeof(int32_t);
+    SCHK(s, hipMemcpyAsync(s->h_rf, s->d_rf_out, nbytes, hipMemcpyDeviceToHost, s->stream));
+    SCHK(s, hipEventRecord(s->ev_rf[2], s->stream));
+    SCHK(s, hipGetLastError());
+    SCHK(s, hipEventSynchronize(s->ev_rf[2]));
+    for (int i = 0; i < 2; ++i)
+        if (hipEventElapsedTime(&s->rf_ms[i], s->ev_rf[0], s->ev_rf[i + 1]) != hipSuccess) s->rf_ms[i] = 0.f;
+    const double *h_sn = s->h_rf, *h_osn = h_sn + (size_t)n * nstep;
+    const int32_t *h_kb = (const int32_t *)(s->h_rf + nd), *h_loc = h_kb + n;
+    if (status) memcpy(status, st.data(), (size_t)n * sizeof(int32_t));
+    if (sn_dm) memcpy(sn_dm, h_sn, (size_t)n * nstep * sizeof(double));
+    if (kbest) memcpy(kbest, h_kb, (size_t)n * sizeof(int32_t));
+    if (opt_sn) memcpy(opt_sn, h_osn, (size_t)n * nw * sizeof(double));
+    if (opt_loc) memcpy(opt_loc, h_loc, (size_t)n * nw * sizeof(int32_t));
+    if (series) memcpy(series, h_kb + ni, ns * sizeof(uint32_t));
+    return PB_OK;
+}
+
+extern "C" int pb_search_refine_timers(const pb_search *s, float *ms2)
+{
+    if (!s || !ms2) return PB_EINVAL;
+    ms2[0] = s->rf_ms[0];
+    ms2[1] = s->rf_ms[1];
     return PB_OK;
 }

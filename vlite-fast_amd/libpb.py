@@ -56,7 +56,8 @@ EXPORTS = ["pb_config_default", "pb_create", "pb_destroy", "pb_last_error", "pb_
            "pb_debug_fetch", "pb_debug_dag_check", "pb_channelize_f32", "pb_version", "pb_search_create", "pb_search_create_list", "pb_search_destroy",
            "pb_search_last_error", "pb_search_info", "pb_search_run", "pb_search_set_baseline", "pb_search_peaks",
            "pb_search_timers", "pb_search_set_rfi", "pb_search_rfi_info", "pb_search_fetch_clean", "pb_search_set_cutouts",
-           "pb_search_cutouts", "pb_search_cutout_timers"]
+           "pb_search_cutouts", "pb_search_cutout_timers", "pb_search_set_refine", "pb_search_refine",
+           "pb_search_refine_timers"]
 
 _lib = None
 
@@ -148,6 +149,10 @@ def load():
     L.pb_search_set_cutouts.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
     L.pb_search_cutouts.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, u32p, u32p, u32p, u32p]
     L.pb_search_cutout_timers.argtypes = [vp, fp]
+    i32p, f64p = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    L.pb_search_set_refine.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.pb_search_refine.argtypes = [vp, i32p, fp, C.c_int, i32p, f64p, i32p, f64p, i32p, u32p]
+    L.pb_search_refine_timers.argtypes = [vp, fp]
     for n in EXPORTS:
         f = getattr(L, n)
         if f.restype is C.c_int or n in ("pb_create", "pb_query", "pb_sync"):

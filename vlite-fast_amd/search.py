@@ -75,6 +75,7 @@ class Searcher(object):
         self.nchan, self.tsamp = nchan, tsamp
         self.fch1, self.foff = fch1, foff
         self._cut = None                 # (nsub, nt, ndmrow, max_cands) once set_cutouts has switched them on
+        self._ref = None                 # (nstep, half_window, wmax, max_cands) once set_refine has switched it on
         self.dms = dm_min + dm_step * np.arange(self.ndm) if dm_list is None else np.asarray(dm_list, np.float64)
         self._nsamp = 0
 
@@ -159,6 +160,97 @@ class Searcher(object):
         """device ms of the last cutouts() call: the kernels; the kernels and the copy to the host"""
         t = (C.c_float * 2)()
         self._L.pb_search_cutout_timers(self._s, t)
+        return dict(kernels=float(t[0]), with_copy=float(t[1]))
+
+    def set_refine(self, nstep=32, half_window=128, wmax=32, max_cands=32):
+        """refinement of candidates on the last block (include/pb_hip.h, pb_search_set_refine): nstep fine trial DMs per
+        request, a window of half_window samples either side of the peak, the odd widths below wmax, up to max_cands
+        requests per refine_raw() call; max_cands=0 switches it off"""
+        rc = self._L.pb_search_set_refine(self._s, int(nstep), int(half_window), int(wmax), int(max_cands))
+        if rc != 0:
+            raise ValueError(self._L.pb_search_last_error(self._s).decode())
+        self._ref = (int(nstep), int(half_window), int(wmax), int(max_cands)) if max_cands else None
+
+    def refine_raw(self, t, width, dm_lo, dm_step, want_series=False):
+        """pb_search_refine on the last block searched, one request per element (scalars or equally long sequences): peak
+        sample t in block coordinates, width in 1..wmax (an even one counts as width + 1), fine trial k at
+        float32(dm_lo) + k float32(dm_step).  Returns dict(status [n], sn_dm [n][nstep] f64 (NaN: trial outside the DM
+        grid), kbest [n], opt_sn [n][wmax/2] f64, opt_loc [n][wmax/2], widths [wmax/2], dm_lo, dm_step [n] as rounded to binary32, dms [n][nstep] the trials' DMs,
+        series? [n][nstep][2 (half_window + wmax/2)] u32)."""
+        if self._ref is None:
+            raise self._lp.PbError("refinement is not switched on: call set_refine() first")
+        nstep, H, wmax, _ = self._ref
+        nw = wmax // 2
+        ri = np.stack(np.broadcast_arrays(np.atleast_1d(t), np.atleast_1d(width)), axis=1)
+        ri = np.ascontiguousarray(ri, np.int32)
+        n = ri.shape[0]
+        rf = np.stack(np.broadcast_arrays(np.atleast_1d(dm_lo), np.atleast_1d(dm_step)), axis=1)
+        rf = np.ascontiguousarray(np.broadcast_to(rf, (n, 2)), np.float32)
+        out = dict(status=np.zeros(n, np.int32), sn_dm=np.full((n, nstep), np.nan), kbest=np.full(n, -1, np.int32),
+                   opt_sn=np.full((n, nw), np.nan), opt_loc=np.full((n, nw), -1, np.int32))
+        ser = np.zeros((n, nstep, 2 * (H + nw)), np.uint32) if want_series else None
+        i32p, f64p = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        rc = self._L.pb_search_refine(self._s, ri.ctypes.data_as(i32p), rf.ctypes.data_as(C.POINTER(C.c_float)), n,
+                                      out["status"].ctypes.data_as(i32p), out["sn_dm"].ctypes.data_as(f64p),
+                                      out["kbest"].ctypes.data_as(i32p), out["opt_sn"].ctypes.data_as(f64p),
+                                      out["opt_loc"].ctypes.data_as(i32p),
+                                      ser.ctypes.data_as(C.POINTER(C.c_uint32)) if want_series else None)
+        if rc != 0:
+            raise self._lp.PbError("pb_search_refine failed (%d): %s" % (rc, self._L.pb_search_last_error(self._s).decode()))
+        out["widths"] = 2 * np.arange(nw) + 1
+        out["dm_lo"], out["dm_step"] = rf[:, 0].astype(np.float64), rf[:, 1].astype(np.float64)
+        out["dms"] = rf[:, :1].astype(np.float64) + np.arange(nstep)[None, :] * rf[:, 1:].astype(np.float64)
+        if want_series:
+            out["series"] = ser
+        return out
+
+    def refine_plan(self, dmi, width_log2):
+        """pass 1 of refine() for a candidate at trial DM index dmi with boxcar 2^width_log2: (width, dm_lo, dm_step).  The
+        fine trials span the grid DM +- the larger gap to its neighbours in the grid; the width is the candidate's,
+        at most wmax."""
+        nstep, _, wmax, _ = self._ref
+        dms = np.asarray(self.dms, np.float64)
+        gaps = [abs(dms[j] - dms[dmi]) for j in (dmi - 1, dmi + 1) if 0 <= j < dms.size]
+        span = max(gaps) if gaps else 1.0
+        return min(1 << int(width_log2), wmax), dms[dmi] - span, 2.0 * span / max(nstep - 1, 1)
+
+    def refine(self, dmi, t, width_log2):
+        """The reference's refinement of a candidate (analysis/loc_step0.py: refine_dm coarse, refine_dm fine,
+        optimize_pulse) on the block that is still on the device, in two refine_raw() calls.  dmi, t, width_log2: a
+        candidate's trial DM index, peak sample in block coordinates and log2 boxcar width, scalars or equally long
+        sequences.  Pass 1: refine_plan().  Pass 2: centred on pass 1's best trial, +- two pass-1 steps.  Per candidate
+        dict(dm, snr, width, peak, trials=[(dms, sns), (dms, sns)], opt_sn, opt_loc): the best fine DM of pass 2 and its
+        S/N; width, and peak (block coordinates), from the largest opt_sn of pass 2's width pass.  None for a candidate
+        whose window is too short or whose trials all lie outside the DM grid.  A scalar request returns one entry, a
+        sequence a list."""
+        if self._ref is None:
+            raise self._lp.PbError("refinement is not switched on: call set_refine() first")
+        nstep, H, _, _ = self._ref
+        scalar = np.ndim(dmi) == 0
+        dmi, t, wl = [np.asarray(v, np.int64) for v in np.broadcast_arrays(np.atleast_1d(dmi), np.atleast_1d(t), np.atleast_1d(width_log2))]
+        plan = [self.refine_plan(int(d), int(w)) for d, w in zip(dmi, wl)]
+        width, lo1, st1 = [np.array(v) for v in zip(*plan)]
+        p1 = self.refine_raw(t, width, lo1, st1)
+        k1 = np.maximum(p1["kbest"], 0)
+        st1 = p1["dm_step"]                                             # the binary32 step that was used
+        lo2 = p1["dms"][np.arange(len(t)), k1] - 2.0 * st1
+        p2 = self.refine_raw(t, width, lo2, 4.0 * st1 / max(nstep - 1, 1))
+        out = []
+        for i in range(len(t)):
+            if p1["status"][i] or p1["kbest"][i] < 0 or p2["kbest"][i] < 0:
+                out.append(None)
+                continue
+            k2, iw = int(p2["kbest"][i]), int(np.argmax(p2["opt_sn"][i]))
+            out.append(dict(dm=float(p2["dms"][i, k2]), snr=float(p2["sn_dm"][i, k2]), width=int(p2["widths"][iw]),
+                            peak=int(max(0, t[i] - H) + p2["opt_loc"][i, iw]),
+                            trials=[(p1["dms"][i], p1["sn_dm"][i]), (p2["dms"][i], p2["sn_dm"][i])],
+                            opt_sn=p2["opt_sn"][i], opt_loc=p2["opt_loc"][i]))
+        return out[0] if scalar else out
+
+    def refine_timers(self):
+        """device ms of the last refine_raw() call: the kernels; the kernels and the copy to the host"""
+        t = (C.c_float * 2)()
+        self._L.pb_search_refine_timers(self._s, t)
         return dict(kernels=float(t[0]), with_copy=float(t[1]))
 
     def timers(self):
@@ -287,11 +379,20 @@ class GulpSearch(object):
     cutouts=dict(thresh=..., max_per_gulp=...) (the searcher's set_cutouts() must be on): of each push()'s or
     finish()'s candidates those at or above thresh, strongest first, at most max_per_gulp (and at most the searcher's
     max_cands), get a "cutout" entry -- dict(ft, ft_hits, dt, dt_hits, dm_rows, sub_freqs, tscr) of Searcher.cutouts
-    with tscr = max(1, width / 2) -- cut from the block that is still on the device.  Nothing else changes."""
+    with tscr = max(1, width / 2) -- cut from the block that is still on the device.  Nothing else changes.
+    refine=dict(thresh=..., max_per_gulp=...) (the searcher's set_refine() must be on): the same selection gets a
+    "refined" entry -- Searcher.refine's dict for the candidate, with `peak` counted from the start of the stream like
+    peak_idx (None where Searcher.refine gives None) -- in the same push() / finish().  Printed and sent lines stay as
+    they are."""
 
     def __init__(self, searcher, threshold=6.0, nbit=8, coincidencer=None, utc_start="1970-01-01-00:00:00", beam=1,
-                 cutouts=None):
+                 cutouts=None, refine=None):
         self.s, self.threshold, self.nbit = searcher, threshold, nbit
+        self.ref = None
+        if refine is not None:
+            if searcher._ref is None:
+                raise ValueError("GulpSearch(refine=...): call the searcher's set_refine() first")
+            self.ref = (float(refine.get("thresh", threshold)), min(int(refine.get("max_per_gulp", 32)), searcher._ref[3]))
         self.cut = None
         if cutouts is not None:
             if searcher._cut is None:
@@ -325,6 +426,18 @@ class GulpSearch(object):
             c["cutout"] = dict(ft=r["ft"][i], ft_hits=r["ft_hits"][i], dt=r["dt"][i], dt_hits=r["dt_hits"][i],
                                dm_rows=r["dm_rows"][i], sub_freqs=r["sub_freqs"], tscr=tscr[i])
 
+    def _refine(self, cands, sample0):
+        """attach the refinement to the strongest candidates; sample0 as in _cutouts"""
+        if self.ref is None:
+            return
+        thresh, most = self.ref
+        sel = [c for c in cands if c["snr"] >= thresh][:most]
+        if not sel:
+            return
+        r = self.s.refine([c["dmi"] for c in sel], [c["peak_idx"] - sample0 for c in sel], [c["tfilt"] for c in sel])
+        for c, e in zip(sel, r):
+            c["refined"] = None if e is None else dict(e, peak=e["peak"] + sample0)
+
     @staticmethod
     def _subset(pk, sel):
         return dict(dmi=pk["dmi"][sel], t=pk["t"][sel], snr=pk["snr"][sel], width_log2=pk["width_log2"][sel])
@@ -345,6 +458,7 @@ class GulpSearch(object):
         self.pending = (self._subset(pk, ~full), self.done, pk["tout"])
         first = self.last_first = self.done
         self._cutouts(cands, first)
+        self._refine(cands, first)
         self.done += nout
         keep = min(self.s.max_delay + self.ov, data.shape[0])
         self.tail = data[data.shape[0] - keep:].copy()
@@ -359,6 +473,7 @@ class GulpSearch(object):
         self.pending = None
         cands = candidates_from_peaks(pk, self.s.dms, self.s.tsamp, sample0=sample0)
         self._cutouts(cands, sample0)              # the block of the last push() is still the searcher's current one
+        self._refine(cands, sample0)
         self.last_first = self.done
         self._send(cands, self.done, tout - (self.done - sample0))
         self.done = sample0 + tout
@@ -395,6 +510,9 @@ def arg_parser():
     ap.add_argument("-cutouts", action="store_true", help="with -output_dir: a .cutouts.npz beside each .cand file")
     ap.add_argument("-cutout_thresh", type=float, default=None, help="with -cutouts: lowest S/N cut out (default: -detect_thresh)")
     ap.add_argument("-cutout_max", type=int, default=32, help="with -cutouts: most cutouts per gulp")
+    ap.add_argument("-refine", action="store_true", help="refine DM, width and S/N of the strongest candidates; with -output_dir a .refined file beside each .cand")
+    ap.add_argument("-refine_thresh", type=float, default=None, help="with -refine: lowest S/N refined (default: -detect_thresh)")
+    ap.add_argument("-refine_max", type=int, default=32, help="with -refine: most refinements per gulp")
     return ap
 
 
@@ -408,6 +526,10 @@ def parse_args(argv=None):
         ap.error("-cutout_max must be >= 1")
     if a.cutout_thresh is None:
         a.cutout_thresh = a.detect_thresh
+    if a.refine_max < 1:
+        ap.error("-refine_max must be >= 1")
+    if a.refine_thresh is None:
+        a.refine_thresh = a.detect_thresh
     return a
 
 
@@ -434,6 +556,22 @@ def write_cutouts_npz(path, cands, tsamp):
     return len(cc)
 
 
+def refined_line(c):
+    """a candidate's line followed by its refined DM, S/N, width (samples) and peak sample (stream index)"""
+    r = c["refined"]
+    return "%s\t%.6f\t%.4f\t%d\t%d" % (candidate_line(c), r["dm"], r["snr"], r["width"], r["peak"])
+
+
+def write_refined(path, cands):
+    """The refined candidates of one gulp (those that carry a refinement), one refined_line each.  Returns how many were
+    written (0: no file)."""
+    cc = [c for c in cands if c.get("refined")]
+    if cc:
+        with open(path, "w") as f:
+            f.write("".join(refined_line(c) + "\n" for c in cc))
+    return len(cc)
+
+
 def gulp_stem(utc_start, first_sample, tsamp, beam):
     """<UTC of the gulp's first sample>_<beam, two digits>: the name heimdall gives a gulp's candidate file, as far as
     this project knows it (unpinned)"""
@@ -449,7 +587,8 @@ def main(argv=None):
     -output_dir /mnt/ssd/cands -cutouts -coincidencer vlite-nrl:27555` (the flags of
     scripts/start_heimdall_single_antenna:21; that launch leaves heimdall's RFI cleaning on, which here is -rfi_clean).
     Prints heimdall-format candidate lines per gulp and, with -coincidencer, sends them there; with -output_dir each
-    gulp that has candidates also gets a .cand file of the same lines, with -cutouts a .cutouts.npz beside it."""
+    gulp that has candidates also gets a .cand file of the same lines, with -cutouts a .cutouts.npz beside it, with
+    -refine a .refined file (the refined candidates' lines, each followed by refined DM, S/N, width and peak sample)."""
     import os
     sig = importlib.import_module(_pkg + ".sigproc")
     a = parse_args(argv)
@@ -475,7 +614,13 @@ def main(argv=None):
         # subbands where 64 does not divide the band
         s.set_cutouts(nsub=64 if nchan % 64 == 0 else 1, nt=min(256, (maxs // 64) & ~1), max_cands=a.cutout_max)
         cut = dict(thresh=a.cutout_thresh, max_per_gulp=a.cutout_max)
-    g = GulpSearch(s, threshold=a.detect_thresh, coincidencer=a.coincidencer, utc_start=utc, beam=a.beam, cutouts=cut)
+    ref = None
+    if a.refine:
+        # the default geometry; a shorter window where the blocks are too short for two of the default
+        s.set_refine(half_window=max(64, min(128, (maxs // 4) & ~1)), max_cands=a.refine_max)
+        ref = dict(thresh=a.refine_thresh, max_per_gulp=a.refine_max)
+    g = GulpSearch(s, threshold=a.detect_thresh, coincidencer=a.coincidencer, utc_start=utc, beam=a.beam, cutouts=cut,
+                   refine=ref)
     if a.output_dir:
         os.makedirs(a.output_dir, exist_ok=True)
     ntot, stems = 0, set()
@@ -492,6 +637,8 @@ def main(argv=None):
                 f.write("".join(candidate_line(c) + "\n" for c in cands))
             if a.cutouts:
                 write_cutouts_npz(os.path.join(a.output_dir, stem + ".cutouts.npz"), cands, tsamp)
+            if a.refine:
+                write_refined(os.path.join(a.output_dir, stem + ".refined"), cands)
         return len(cands)
 
     with open(a.fil, "rb") as f:
