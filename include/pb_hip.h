@@ -454,6 +454,67 @@ int pb_search_refine(pb_search *s, const int32_t *req_i2, const float *req_f2, i
 /* device time of the last pb_search_refine in ms: the three kernels; the kernels and the copy to the host */
 int pb_search_refine_timers(const pb_search *s, float *ms2);
 
+/* Giants and clusters of giants: the last run's S/N planes turned into candidates on the device, the step heimdall
+ * takes after its matched filter (its giant finder and its labelling of giants over -cand_sep_time / -cand_sep_dm /
+ * -cand_sep_filter).  heimdall's source is third-party and absent: what follows is THIS project's definition, exact,
+ * independent of the order anything runs in, and bounded in memory; parity with heimdall's list stays unpinned.  Off
+ * until pb_search_set_giants; a pb_search on which it was never called allocates nothing more, launches nothing more
+ * and returns what it returns without it.
+ * Inputs: the planes snr[d][t] (binary32) and wl[d][t] (log2 width, u8) of the last pb_search_run / pb_search_peaks (or of
+ * pb_search_set_planes), d in [0, ndm), t in [0, tout); a threshold, binary32; a sample range 0 <= t_lo < t_hi <= tout;
+ * sep_time in 1..64, sep_dm >= 0 (in trial-DM indices), sep_filter >= 0 (3 / 200 / 3 by default in search.py: heimdall's
+ * defaults as far as known, unpinned).
+ * Giants:
+ *   1. A sample is hot when t_lo <= t < t_hi and snr[d][t] >= thresh, compared in binary32; a NaN is not hot.
+ *   2. A giant is a maximal set of hot samples of one series in which consecutive hot samples are at most sep_time apart.
+ *   3. Its fields: dmi; begin, the first hot sample; end, the last hot sample + 1; npts, the number of hot samples;
+ *      peak, the hot sample with the largest S/N, the smallest t among equals (-0 equals +0); snr = snr[dmi][peak], bit
+ *      for bit; tfilt = wl[dmi][peak].
+ *   4. The giant list is in ascending (dmi, begin) order, whatever order the workgroups ran in.
+ * Links and clusters:
+ *   5. Giants a and b are linked when |dmi_a - dmi_b| <= sep_dm, |tfilt_a - tfilt_b| <= sep_filter,
+ *      begin_a < end_b + sep_time and begin_b < end_a + sep_time.  Two giants of one series therefore never link directly.
+ *   6. Clusters are the connected components of that relation.  A cluster's label is its smallest member index.
+ * Candidates:
+ *   7. One candidate per cluster.  The member with the largest S/N gives snr, peak, tfilt and dmi; ties go to the smallest
+ *      giant index.
+ *   8. members is the number of giants in the cluster, npoints the sum of their npts, i0 the smallest begin, i1 the largest
+ *      end.
+ *   9. The device table is in label order.  The host (search.py) sorts it strongest first, ties broken by (dmi, peak).
+ * Overflow:
+ *  10. If the number of giants G exceeds max_giants the call succeeds, reports G exactly and an overflow flag, and returns
+ *      no candidates (heimdall's -max_giant_rate behaviour: the gulp is given up, deterministically).  G is known from a
+ *      counting pass before anything is written.
+ * Gulps:
+ *  11. A run of hot samples cut by t_hi (or t_lo) is two giants in two calls: a call knows nothing of samples outside its
+ *      range.
+ * No floating-point arithmetic takes part, only comparisons of binary32 values: tests/search_giants_ref.py restates this
+ * in NumPy and tests/test_gpu_search_giants.py holds the kernels to it field by field, exactly.
+ * A giant is PB_GIANT_WORDS int32: dmi, begin, end, npts, peak, S/N bits, tfilt, label.  A candidate is PB_GIANT_WORDS
+ * int32: S/N bits, peak, tfilt, dmi, members, npoints, i0, i1.
+ * pb_search_set_giants allocates the device and page-locked host buffers for up to max_giants giants per call;
+ * max_giants = 0 frees them and switches the stage off.  PB_EINVAL with nothing changed for sep_time outside 1..64, a
+ * negative sep_dm or sep_filter, max_giants outside 0..2^22, or ndm x max_samples >= 2^31 (the counts are 32-bit). */
+#define PB_GIANT_WORDS 8
+int pb_search_set_giants(pb_search *s, int sep_time, int sep_dm, int sep_filter, int max_giants);
+/* On the planes that are on the device: cands (host) receives min(*ncands, max_out) candidates in label order; *ngiants =
+ * G, *overflow = 1 when G > max_giants (then *ncands = 0).  Runs on the search's stream; the host waits once for G (it
+ * sizes the grids) and once per labelling sweep for the "a label changed" word; the results come back in one copy through
+ * page-locked memory.  PB_EINVAL before anything is launched or written when the stage is off, there are no planes yet, the
+ * range is bad, the threshold is a NaN or an output pointer is missing (message: pb_search_last_error). */
+int pb_search_giants(pb_search *s, float thresh, int t_lo, int t_hi, int32_t *cands, int max_out, int *ncands, int *ngiants,
+                     int *overflow);
+/* the giants of the last pb_search_giants with their labels (none after an overflow): out receives min(*n, max_out) of
+ * them; for tests and diagnostics */
+int pb_search_giant_list(pb_search *s, int32_t *out, int max_out, int *n);
+/* Replaces the planes on the device with host planes snr, width_log2 [ndm][tout], 1 <= tout <= max_samples: stored planes
+ * can be clustered again, and tests put hand-made patterns in front of the kernels.  The block, its dedispersed series
+ * and what cutouts and refinement read stay as the last run left them. */
+int pb_search_set_planes(pb_search *s, const float *snr, const uint8_t *width_log2, int tout);
+/* the last pb_search_giants: device time in ms of the giant pass (count, scan, write), of the labelling and the merge,
+ * and of everything with the copy to the host; *nsweeps (may be NULL) = hook / jump sweeps of the labelling */
+int pb_search_giant_timers(const pb_search *s, float *ms3, int *nsweeps);
+
 /* Page-locked host memory for the blocks handed to pb_submit_vdif(_at) (H2D copies from pageable memory are
  * staged and synchronous); the reference allocates its 1-s host buffer the same way (cudaMallocHost,
  * src/process_baseband.cu:579).  A host program above this ABI needs no HIP headers.  NULL on failure. */

@@ -57,7 +57,8 @@ EXPORTS = ["pb_config_default", "pb_create", "pb_destroy", "pb_last_error", "pb_
            "pb_search_last_error", "pb_search_info", "pb_search_run", "pb_search_set_baseline", "pb_search_peaks",
            "pb_search_timers", "pb_search_set_rfi", "pb_search_rfi_info", "pb_search_fetch_clean", "pb_search_set_cutouts",
            "pb_search_cutouts", "pb_search_cutout_timers", "pb_search_set_refine", "pb_search_refine",
-           "pb_search_refine_timers"]
+           "pb_search_refine_timers", "pb_search_set_giants", "pb_search_giants", "pb_search_giant_list",
+           "pb_search_set_planes", "pb_search_giant_timers"]
 
 _lib = None
 
@@ -153,6 +154,11 @@ def load():
     L.pb_search_set_refine.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
     L.pb_search_refine.argtypes = [vp, i32p, fp, C.c_int, i32p, f64p, i32p, f64p, i32p, u32p]
     L.pb_search_refine_timers.argtypes = [vp, fp]
+    L.pb_search_set_giants.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.pb_search_giants.argtypes = [vp, C.c_float, C.c_int, C.c_int, i32p, C.c_int, ip, ip, ip]
+    L.pb_search_giant_list.argtypes = [vp, i32p, C.c_int, ip]
+    L.pb_search_set_planes.argtypes = [vp, fp, u8p, C.c_int]
+    L.pb_search_giant_timers.argtypes = [vp, fp, ip]
     for n in EXPORTS:
         f = getattr(L, n)
         if f.restype is C.c_int or n in ("pb_create", "pb_query", "pb_sync"):

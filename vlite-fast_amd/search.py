@@ -76,8 +76,10 @@ class Searcher(object):
         self.fch1, self.foff = fch1, foff
         self._cut = None                 # (nsub, nt, ndmrow, max_cands) once set_cutouts has switched them on
         self._ref = None                 # (nstep, half_window, wmax, max_cands) once set_refine has switched it on
+        self._gi = None                  # (sep_time, sep_dm, sep_filter, max_giants) once set_giants has switched it on
         self.dms = dm_min + dm_step * np.arange(self.ndm) if dm_list is None else np.asarray(dm_list, np.float64)
         self._nsamp = 0
+        self._tout = 0
 
     def close(self):
         if getattr(self, "_s", None):
@@ -253,6 +255,67 @@ class Searcher(object):
         self._L.pb_search_refine_timers(self._s, t)
         return dict(kernels=float(t[0]), with_copy=float(t[1]))
 
+    def set_giants(self, sep_time=3, sep_dm=200, sep_filter=3, max_giants=1 << 18):
+        """giants and clusters of giants on the device (include/pb_hip.h, pb_search_set_giants): hot samples of a series
+        at most sep_time apart make a giant, giants within sep_dm trial DMs, sep_filter in log2 width and sep_time in time
+        are linked, up to max_giants giants per giants() call; max_giants=0 switches the stage off"""
+        rc = self._L.pb_search_set_giants(self._s, int(sep_time), int(sep_dm), int(sep_filter), int(max_giants))
+        if rc != 0:
+            raise ValueError(self._L.pb_search_last_error(self._s).decode())
+        self._gi = (int(sep_time), int(sep_dm), int(sep_filter), int(max_giants)) if max_giants else None
+
+    def set_planes(self, snr, width_log2):
+        """replace the S/N and log2-width planes on the device with host planes [ndm][tout] (stored planes clustered
+        again; hand-made patterns for tests); giants() then acts on them"""
+        snr = np.ascontiguousarray(snr, np.float32)
+        wl = np.ascontiguousarray(width_log2, np.uint8)
+        if snr.ndim != 2 or snr.shape[0] != self.ndm or wl.shape != snr.shape:
+            raise ValueError("set_planes: both planes must be [ndm][tout]")
+        rc = self._L.pb_search_set_planes(self._s, snr.ctypes.data_as(C.POINTER(C.c_float)),
+                                          wl.ctypes.data_as(C.POINTER(C.c_uint8)), snr.shape[1])
+        if rc != 0:
+            raise ValueError(self._L.pb_search_last_error(self._s).decode())
+        self._tout = snr.shape[1]
+
+    def giants(self, thresh, t_lo=0, t_hi=None, want_list=False):
+        """pb_search_giants on the planes of the last run()/peaks() (or set_planes()), samples [t_lo, t_hi) (t_hi None: to
+        the planes' end).  Returns dict(snr f32, peak, tfilt, dmi, members, npoints, i0, i1 -- one entry per cluster, in
+        label order --, ngiants, overflow; with want_list also giant_list = dict(dmi, begin, end, npts, peak, snr, tfilt,
+        label), ascending (dmi, begin)).  After an overflow (ngiants > max_giants) every array is empty."""
+        if self._gi is None:
+            raise self._lp.PbError("giants are not switched on: call set_giants() first")
+        if t_hi is None:
+            t_hi = self._tout
+        cap = self._gi[3]
+        i32p, ip = C.POINTER(C.c_int32), C.POINTER(C.c_int)
+        nc, ng, ov = C.c_int(), C.c_int(), C.c_int()
+        buf = np.empty((cap, 8), np.int32)
+        rc = self._L.pb_search_giants(self._s, C.c_float(thresh), int(t_lo), int(t_hi), buf.ctypes.data_as(i32p), cap,
+                                      C.byref(nc), C.byref(ng), C.byref(ov))
+        if rc != 0:
+            raise self._lp.PbError("pb_search_giants failed (%d): %s" % (rc, self._L.pb_search_last_error(self._s).decode()))
+        b = buf[:nc.value]
+        out = dict(snr=b[:, 0].copy().view(np.float32), peak=b[:, 1].copy(), tfilt=b[:, 2].copy(), dmi=b[:, 3].copy(),
+                   members=b[:, 4].copy(), npoints=b[:, 5].copy(), i0=b[:, 6].copy(), i1=b[:, 7].copy(),
+                   ngiants=ng.value, overflow=bool(ov.value))
+        if want_list:
+            n = C.c_int()
+            g = np.empty((0 if ov.value else ng.value, 8), np.int32)
+            rc = self._L.pb_search_giant_list(self._s, g.ctypes.data_as(i32p), g.shape[0], C.byref(n))
+            if rc != 0:
+                raise self._lp.PbError("pb_search_giant_list failed (%d): %s" % (rc, self._L.pb_search_last_error(self._s).decode()))
+            out["giant_list"] = dict(dmi=g[:, 0].copy(), begin=g[:, 1].copy(), end=g[:, 2].copy(), npts=g[:, 3].copy(),
+                                     peak=g[:, 4].copy(), snr=g[:, 5].copy().view(np.float32), tfilt=g[:, 6].copy(),
+                                     label=g[:, 7].copy())
+        return out
+
+    def giant_timers(self):
+        """the last giants() call: device ms of the giant pass, of the labelling and merge, of everything with the copy;
+        and the labelling's sweeps"""
+        t, n = (C.c_float * 3)(), C.c_int()
+        self._L.pb_search_giant_timers(self._s, t, C.byref(n))
+        return dict(giants=float(t[0]), label=float(t[1]), with_copy=float(t[2]), sweeps=int(n.value))
+
     def timers(self):
         """device ms of the last run's stages"""
         t = (C.c_float * 6)()
@@ -276,6 +339,7 @@ class Searcher(object):
         if rc != 0:
             raise self._lp.PbError("pb_search_peaks failed (%d): %s" % (rc, self._L.pb_search_last_error(self._s).decode()))
         self._nsamp = nsamp
+        self._tout = t.value
         k = min(n.value, max_out, 1 << 20)        # (the device list holds 2^20 points)
         b = buf[:k]
         return dict(dmi=b[:, 0].copy(), t=b[:, 1].copy(), snr=b[:, 2].copy().view(np.float32), width_log2=b[:, 3].astype(np.uint8),
@@ -301,6 +365,7 @@ class Searcher(object):
         if rc != 0:
             raise self._lp.PbError("pb_search_run failed (%d): %s" % (rc, self._L.pb_search_last_error(self._s).decode()))
         self._nsamp = nsamp
+        self._tout = tout
         return dict(snr=snr, width_log2=wid, stats=stats, series=series, tout=tout)
 
 
@@ -364,6 +429,21 @@ def candidates_from_peaks(pk, dms, tsamp, dm_tol=0.1, sample0=0, delta_w=None):
     return group_points(pk["dmi"], pk["t"], pk["snr"], 1 << pk["width_log2"].astype(np.int64), dms, tsamp, dm_tol, delta_w, sample0)
 
 
+def candidates_from_giants(res, dms, tsamp, sample0=0):
+    """Searcher.giants' clusters as candidates: the dicts of group_points (ngiant = the cluster's giants) plus npoints,
+    strongest first, ties broken by (DM index, peak).  The clustering is the device's (include/pb_hip.h,
+    pb_search_set_giants), connected components of linked giants: exact and independent of any arrival order."""
+    if len(res["snr"]) == 0:
+        return []
+    sn = np.asarray(res["snr"], np.float32)
+    order = np.lexsort((res["peak"], res["dmi"], -sn.astype(np.float64)))
+    dms = np.asarray(dms)
+    return [dict(snr=float(sn[k]), peak_idx=int(sample0 + res["peak"][k]), peak_time=float((sample0 + res["peak"][k]) * tsamp),
+                 tfilt=int(res["tfilt"][k]), dmi=int(res["dmi"][k]), dm=float(dms[res["dmi"][k]]),
+                 ngiant=int(res["members"][k]), i0=int(sample0 + res["i0"][k]), i1=int(sample0 + res["i1"][k]),
+                 npoints=int(res["npoints"][k])) for k in order]
+
+
 class GulpSearch(object):
     """The search over a stream of filterbank samples in gulps, as heimdall runs it (-nsamps_gulp 30720,
     scripts/start_heimdall_single_antenna:21): every gulp is searched together with the last
@@ -383,11 +463,19 @@ class GulpSearch(object):
     refine=dict(thresh=..., max_per_gulp=...) (the searcher's set_refine() must be on): the same selection gets a
     "refined" entry -- Searcher.refine's dict for the candidate, with `peak` counted from the start of the stream like
     peak_idx (None where Searcher.refine gives None) -- in the same push() / finish().  Printed and sent lines stay as
-    they are."""
+    they are.
+    giants=dict(sep_time=..., sep_dm=..., sep_filter=..., max_giants=...) (any subset; {} for the defaults): the
+    candidates come from the device's giants and clusters (Searcher.set_giants / giants, candidates_from_giants) instead
+    of the point list and group_points; the point list is not pulled at all.  A gulp with more than max_giants giants
+    yields no candidates and one log line.  A run of hot samples cut by the end of a gulp's complete samples is two
+    giants, one in each gulp's call."""
 
     def __init__(self, searcher, threshold=6.0, nbit=8, coincidencer=None, utc_start="1970-01-01-00:00:00", beam=1,
-                 cutouts=None, refine=None):
+                 cutouts=None, refine=None, giants=None):
         self.s, self.threshold, self.nbit = searcher, threshold, nbit
+        self.gi = giants is not None
+        if self.gi:
+            searcher.set_giants(**giants)
         self.ref = None
         if refine is not None:
             if searcher._ref is None:
@@ -438,6 +526,16 @@ class GulpSearch(object):
         for c, e in zip(sel, r):
             c["refined"] = None if e is None else dict(e, peak=e["peak"] + sample0)
 
+    def _giants(self, t_lo, t_hi, sample0):
+        """the candidates of the current block's samples [t_lo, t_hi) from the device's giants"""
+        res = self.s.giants(self.threshold, t_lo, t_hi)
+        if res["overflow"]:
+            import sys
+            sys.stderr.write("search: gulp at sample %d given up: %d giants exceed max_giants %d\n"
+                             % (sample0 + t_lo, res["ngiants"], self.s._gi[3]))
+            return []
+        return candidates_from_giants(res, self.s.dms, self.s.tsamp, sample0=sample0)
+
     @staticmethod
     def _subset(pk, sel):
         return dict(dmi=pk["dmi"][sel], t=pk["t"][sel], snr=pk["snr"][sel], width_log2=pk["width_log2"][sel])
@@ -451,11 +549,18 @@ class GulpSearch(object):
         if data.shape[0] - self.s.max_delay < 64 + self.ov:
             self.tail = data                          # not enough yet for one output block
             return []
-        pk = self.s.peaks(data, self.threshold, nbit=8)
-        nout = pk["tout"] - self.ov                   # samples with every width tried
-        full = pk["t"] < nout
-        cands = candidates_from_peaks(self._subset(pk, full), self.s.dms, self.s.tsamp, sample0=self.done)
-        self.pending = (self._subset(pk, ~full), self.done, pk["tout"])
+        if self.gi:
+            # the same entry with a threshold no sample reaches: the block is searched, no point comes back
+            pk = self.s.peaks(data, float("inf"), nbit=8, max_out=1)
+            nout = pk["tout"] - self.ov
+            cands = self._giants(0, nout, self.done)
+            self.pending = (nout, self.done, pk["tout"])
+        else:
+            pk = self.s.peaks(data, self.threshold, nbit=8)
+            nout = pk["tout"] - self.ov                   # samples with every width tried
+            full = pk["t"] < nout
+            cands = candidates_from_peaks(self._subset(pk, full), self.s.dms, self.s.tsamp, sample0=self.done)
+            self.pending = (self._subset(pk, ~full), self.done, pk["tout"])
         first = self.last_first = self.done
         self._cutouts(cands, first)
         self._refine(cands, first)
@@ -471,7 +576,10 @@ class GulpSearch(object):
             return []
         pk, sample0, tout = self.pending
         self.pending = None
-        cands = candidates_from_peaks(pk, self.s.dms, self.s.tsamp, sample0=sample0)
+        if self.gi:                                # pk: the first sample of the block that push() left out
+            cands = self._giants(pk, tout, sample0) if pk < tout else []
+        else:
+            cands = candidates_from_peaks(pk, self.s.dms, self.s.tsamp, sample0=sample0)
         self._cutouts(cands, sample0)              # the block of the last push() is still the searcher's current one
         self._refine(cands, sample0)
         self.last_first = self.done
@@ -513,6 +621,11 @@ def arg_parser():
     ap.add_argument("-refine", action="store_true", help="refine DM, width and S/N of the strongest candidates; with -output_dir a .refined file beside each .cand")
     ap.add_argument("-refine_thresh", type=float, default=None, help="with -refine: lowest S/N refined (default: -detect_thresh)")
     ap.add_argument("-refine_max", type=int, default=32, help="with -refine: most refinements per gulp")
+    ap.add_argument("-giants", action="store_true", help="candidates from giants and clusters of giants made on the GPU instead of the host's grouping of points")
+    ap.add_argument("-cand_sep_time", type=int, default=3, help="with -giants: samples between hot samples of one giant, and between linked giants (1..64)")
+    ap.add_argument("-cand_sep_dm", type=int, default=200, help="with -giants: trial DMs between linked giants")
+    ap.add_argument("-cand_sep_filter", type=int, default=3, help="with -giants: log2 boxcar widths between linked giants")
+    ap.add_argument("-max_giants", type=int, default=1 << 18, help="with -giants: a gulp with more giants is given up")
     return ap
 
 
@@ -530,6 +643,12 @@ def parse_args(argv=None):
         ap.error("-refine_max must be >= 1")
     if a.refine_thresh is None:
         a.refine_thresh = a.detect_thresh
+    if not 1 <= a.cand_sep_time <= 64:
+        ap.error("-cand_sep_time must be in 1..64")
+    if a.cand_sep_dm < 0 or a.cand_sep_filter < 0:
+        ap.error("-cand_sep_dm and -cand_sep_filter must be >= 0")
+    if not 1 <= a.max_giants <= 1 << 22:
+        ap.error("-max_giants must be in 1..4194304")
     return a
 
 
@@ -584,11 +703,13 @@ def gulp_stem(utc_start, first_sample, tsamp, beam):
 def main(argv=None):
     """heimdall's place in the chain for a SIGPROC file: `python -m vlite-fast_amd.search -f obs_kur.fil
     -dm 2 1000 -boxcar_max 64 -nsamps_gulp 30720 -zap_chans 0 190 -zap_chans 3900 4096 -rfi_clean
-    -output_dir /mnt/ssd/cands -cutouts -coincidencer vlite-nrl:27555` (the flags of
+    -giants -output_dir /mnt/ssd/cands -cutouts -coincidencer vlite-nrl:27555` (the flags of
     scripts/start_heimdall_single_antenna:21; that launch leaves heimdall's RFI cleaning on, which here is -rfi_clean).
     Prints heimdall-format candidate lines per gulp and, with -coincidencer, sends them there; with -output_dir each
     gulp that has candidates also gets a .cand file of the same lines, with -cutouts a .cutouts.npz beside it, with
-    -refine a .refined file (the refined candidates' lines, each followed by refined DM, S/N, width and peak sample)."""
+    -refine a .refined file (the refined candidates' lines, each followed by refined DM, S/N, width and peak sample).
+    -giants takes the candidates from the GPU's giants and clusters (heimdall's -cand_sep_time / -cand_sep_dm /
+    -cand_sep_filter; this project's own definition) instead of the host's grouping of the point list."""
     import os
     sig = importlib.import_module(_pkg + ".sigproc")
     a = parse_args(argv)
@@ -619,8 +740,10 @@ def main(argv=None):
         # the default geometry; a shorter window where the blocks are too short for two of the default
         s.set_refine(half_window=max(64, min(128, (maxs // 4) & ~1)), max_cands=a.refine_max)
         ref = dict(thresh=a.refine_thresh, max_per_gulp=a.refine_max)
+    gi = dict(sep_time=a.cand_sep_time, sep_dm=a.cand_sep_dm, sep_filter=a.cand_sep_filter,
+              max_giants=a.max_giants) if a.giants else None
     g = GulpSearch(s, threshold=a.detect_thresh, coincidencer=a.coincidencer, utc_start=utc, beam=a.beam, cutouts=cut,
-                   refine=ref)
+                   refine=ref, giants=gi)
     if a.output_dir:
         os.makedirs(a.output_dir, exist_ok=True)
     ntot, stems = 0, set()
