@@ -1,4 +1,4 @@
-"""The search's normalisation on the GPU (k_prefix, k_series_stats, baseline_at, k_boxcar of csrc/pb_search.hip) against
+"""The search's normalisation on the GPU (k_prefix, k_series_stats, baseline_at, k_boxcar of csrc/search_run.hip) against
 the restatement of its definition (include/pb_hip.h under pb_search_set_baseline; tests/search_stats_ref.py, exact
 integer sums and float64 planes; held to independent answers by tests/test_search_stats_cpu.py).
 

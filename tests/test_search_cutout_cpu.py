@@ -41,12 +41,14 @@ def test_refusals_that_need_no_device():
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
 def test_cutout_kernels_use_no_scratch():
-    u = _usage("pb_search.hip")
+    u = _usage("search_cutout.hip")
     for name in ("k_cutout_ft", "k_cutout_dt"):
         k = next(v for sym, v in u.items() if name in sym)
         assert k["ScratchSize"] == 0 and k["Occupancy"] >= 4, (name, k)
-    # every kernel of the search stays scratch-free
-    assert all(v["ScratchSize"] == 0 for v in u.values()), u
+    # every kernel of the search stays scratch-free: the other three translation units as well
+    for src in ("search_run.hip", "search_refine.hip", "search_giants.hip"):
+        u.update(_usage(src))
+    assert len(u) == 20 and all(v["ScratchSize"] == 0 for v in u.values()), u
 
 
 # the hand-made block: 4 channels x 40 samples, xt[c][t] = 40 c + t; two trial DMs with delays 0,0,0,0 and 0,1,2,4:

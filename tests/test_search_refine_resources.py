@@ -14,7 +14,7 @@ FLAGS = ("-O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-fast-math 
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
 def test_refinement_kernels_use_no_scratch():
-    r = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["pb_search.hip"], cwd=CSRC, stdout=subprocess.PIPE,
+    r = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["search_refine.hip"], cwd=CSRC, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     use, cur = {}, None
@@ -30,6 +30,5 @@ def test_refinement_kernels_use_no_scratch():
         k = [v for sym, v in use.items() if name in sym]
         assert len(k) == 1, name
         assert k[0]["ScratchSize"] == 0 and k[0]["LDSByteSize"] <= 32 * 1024 and k[0]["Occupancy"] >= 4, (name, k[0])
-    src = open(os.path.join(CSRC, "pb_search.hip")).read()
-    sec = src[src.index("// ---- refinement of a candidate"):]
+    sec = open(os.path.join(CSRC, "search_refine.hip")).read()
     assert "k_refine_series" in sec and "k_refine_width" in sec and "asm" not in sec

@@ -46,7 +46,7 @@ def test_cli_rfi_flags():
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
 def test_cleaning_kernels_use_no_scratch():
-    u = _usage("pb_search.hip")
+    u = _usage("search_run.hip")
     for name in ("k_rfi_narrow", "k_rfi_broad_list", "k_rfi_broad_mask"):
         k = next(v for sym, v in u.items() if name in sym)
         assert k["ScratchSize"] == 0 and k["Occupancy"] >= 4, (name, k)

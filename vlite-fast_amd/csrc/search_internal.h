@@ -1,0 +1,170 @@
+// What the search's translation units share on the host side: the handle, the dispersion delay, the error and timer
+// helpers, and each stage's free function.  search_run.hip holds the core (create .. fetch_clean) and the RFI cleaning;
+// search_cutout.hip, search_refine.hip and search_giants.hip one optional stage each, kernels and host side together (a
+// kernel lives in the file that launches it).  Device-only helpers: search_dev.h.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <initializer_list>
+#include <string>
+#include <vector>
+
+#include "pb_hip.h"
+
+#define SEARCH_LOCAL __attribute__((visibility("hidden")))      // shared between the search's files, not exported
+
+// Every member has a default initialiser: new pb_search() is a valid handle with every stage off, and a stage's free
+// function ends with `s->stage = {}`.
+struct pb_search {
+    int device = 0, nchan = 0, max_samples = 0, ndm = 0, nbox = 0;
+    float fch1 = 0.f, foff = 0.f, tsamp = 0.f;
+    double dm_last = 0, ftop = 0;          // the grid's last trial DM; the delays' reference frequency (top of the band, MHz)
+    int max_delay = 0;
+    uint8_t *d_codes = nullptr, *d_xt = nullptr;       // raw block; channel-major [nchan][tpitch]
+    int32_t *d_delay = nullptr;            // [ndm][nact] delays of the channels that are not zapped
+    int32_t *d_chans = nullptr;            // [nact] their indices
+    int nact = 0;
+    uint32_t *d_D = nullptr;               // [ndm][max_samples]
+    float *d_stats = nullptr;              // [ndm][2] mean, rms
+    float *d_snr = nullptr;                // [ndm][max_samples]
+    uint8_t *d_wid = nullptr;              // [ndm][max_samples] log2 width
+    uint64_t *d_P = nullptr;               // [ndm][ppitch()] prefix sums of D (P[0] = 0)
+    int32_t *d_peaks = nullptr;            // [1 + 4 * max_peaks]: count, then (dm index, sample, S/N bits, log2 width)
+    int max_peaks = 1 << 20;
+    int baseline = 0;                      // running-baseline window in samples (0: one clipped mean per DM series)
+    int last_tout = 0, last_nsamp = 0;     // last run: output samples, block length
+    int plane_tout = 0;                    // tout of the planes in d_snr / d_wid (the last run's, or pb_search_set_planes')
+    float ms[6] = {};                      // last run: H2D, transpose, dedisperse, prefix + statistics, boxcar, D2H
+    hipEvent_t ev[7] = {};
+    size_t tpitch = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+    size_t ppitch() const { return tpitch + 8; }       // pitch of a row of prefix sums
+
+    // RFI cleaning (pb_search_set_rfi); the buffers exist once it has been switched on
+    struct {
+        int narrow = 0, broad = 0, nbox = 5;
+        float tol = 5.0f;
+        int ran = 0;                       // whether the last run was cleaned
+        int32_t *d_zdelay = nullptr;       // [nact] zeros: k_dedisperse at DM 0 gives the zero-DM series
+        uint8_t *d_med = nullptr;          // [nact] median code of each unzapped channel
+        uint32_t *d_z = nullptr;           // [tpitch] zero-DM series
+        uint64_t *d_zP = nullptr;          // [ppitch()] its prefix sums
+        float *d_zstats = nullptr, *d_zsnr = nullptr;  // [2], [tpitch]
+        uint8_t *d_zwid = nullptr;         // [tpitch]
+        int32_t *d_tlist = nullptr;        // [tpitch] flagged samples of the broad pass
+        unsigned long long *d_rcnt = nullptr;          // [2]: narrow flags, broad samples
+        hipEvent_t ev[1] = {};             // end of cleaning (it starts at the core's ev[2])
+        uint64_t n_narrow = 0;
+        int n_broad = 0;
+        float ms = 0.f;
+    } rfi;
+    // cutouts (pb_search_set_cutouts); the buffers exist while it is switched on (max > 0)
+    struct {
+        int nsub = 0, nt = 0, ndmrow = 0, max = 0;
+        int32_t *d_req = nullptr;          // [max][3] requests: DM index, peak sample, time-scrunch factor
+        int32_t *d_sub = nullptr;          // [nsub][2] each subband's run [first, last) of chans[]
+        uint32_t *d_out = nullptr;         // one call's outputs (cut_layout)
+        uint32_t *h_out = nullptr;         // page-locked: the same, then the requests
+        hipEvent_t ev[3] = {};             // start, kernels done, copy done
+        float ms[2] = {};                  // last call: kernels, kernels + D2H copy
+    } cut;
+    // refinement (pb_search_set_refine); the buffers exist while it is switched on (max > 0)
+    struct {
+        int nstep = 0, H = 0, wmax = 0, max = 0;
+        double *d_g = nullptr;             // [nact] f^-2 - ftop^-2 of each unzapped channel (delay_chan_term)
+        int32_t *d_reqi = nullptr;         // [max][4] requests: peak sample, odd width, status, 0
+        float *d_reqf = nullptr;           // [max][2] dm_lo, dm_step
+        int32_t *d_out = nullptr;          // one call's outputs (refine_layout)
+        int32_t *h_out = nullptr;          // page-locked: the same, then the requests
+        hipEvent_t ev[3] = {};             // start, kernels done, copy done
+        float ms[2] = {};                  // last call: kernels, kernels + D2H copy
+    } rf;
+    // giants and clusters (pb_search_set_giants); the buffers exist while the stage is switched on (max > 0)
+    struct {
+        int sep_time = 0, sep_dm = 0, sep_filter = 0, max = 0;
+        int last = 0;                      // giants of the last pb_search_giants that are in d_giants (0 after an overflow)
+        int sweeps = 0;                    // hook / jump sweeps of the last call
+        int32_t *d_cnt = nullptr, *d_row = nullptr;    // [ndm] giants per series; [ndm + 1] their exclusive sums = each row's first giant
+        int32_t *d_giants = nullptr;       // [max][8] the giants, ascending (dmi, begin)
+        int32_t *d_lab = nullptr;          // [max] labels
+        unsigned long long *d_best = nullptr;          // [max] per label: the largest (S/N key, ~member index)
+        int32_t *d_acc = nullptr;          // [max][4] per label: members, points, INT_MAX - smallest begin, largest end
+        int32_t *d_tile = nullptr;         // [ntile] roots per 256 giants, then [ntile + 1] their exclusive sums
+        int32_t *d_out = nullptr;          // [16] control words (G, overflow, candidates, changed), then [max][8] the candidates
+        int32_t *h_out = nullptr;          // page-locked: the same
+        hipEvent_t ev[4] = {};             // start, giants written, candidates made, copy done
+        float ms[3] = {};                  // last call: giant pass, labelling + merge, everything with the copy
+    } gi;
+};
+
+// The dispersion delay of one channel in samples, in double: 4.148808e3 MHz^2 s (src/candidate.py:33) x DM x
+// (f^-2 - ftop^-2) / tsamp, rounded half up.  The ONE place it is written: the trial DMs' table (search_create, host) and
+// the fine trials of the refinement (k_refine_series, device) both come from here; IEEE double, no contraction.
+static __host__ __device__ inline double delay_chan_term(double f, double ftop) { return 1.0 / (f * f) - 1.0 / (ftop * ftop); }
+static __host__ __device__ inline int32_t delay_samples(double dm, double chan_term, double tsamp)
+{
+    const double d = 4.148808e3 * dm * chan_term / tsamp;
+    return (int32_t)floor(d + 0.5);
+}
+
+extern SEARCH_LOCAL std::string g_search_err;      // the error of a call that has no handle to keep it in
+
+// "<fn>: <what>" becomes the handle's last error (the global one without a handle); returns PB_EINVAL
+static inline int search_fail(pb_search *s, const char *fn, const std::string &what)
+{
+    (s ? s->err : g_search_err) = std::string(fn) + ": " + what;
+    return PB_EINVAL;
+}
+
+#define SCHK(s, call)                                                         \
+    do {                                                                      \
+        hipError_t e_ = (call);                                               \
+        if (e_ != hipSuccess) {                                               \
+            (s)->err = std::string(#call) + ": " + hipGetErrorString(e_);     \
+            return PB_EHIP;                                                   \
+        }                                                                     \
+    } while (0)
+
+// The opening checks of a stage's entry point: a handle, the stage switched on, something to work on.  `on` and `ready`
+// are written `s && ...` by the caller.  PB_OK, or the error recorded by search_fail.
+static inline int search_enter(pb_search *s, const char *fn, bool on, const char *off_msg, bool ready, const char *idle_msg)
+{
+    if (!s) return search_fail(nullptr, fn, "no search handle");
+    if (!on) return search_fail(s, fn, off_msg);
+    if (!ready) return search_fail(s, fn, idle_msg);
+    return PB_OK;
+}
+
+// device ms from event a to event b, 0 if either was not recorded
+static inline float search_ms(hipEvent_t a, hipEvent_t b)
+{
+    float ms = 0.f;
+    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.f;
+}
+
+// the body of every *_timers getter
+static inline int search_get_ms(const pb_search *s, const float *ms, int n, float *out)
+{
+    if (!s || !out) return PB_EINVAL;
+    for (int i = 0; i < n; ++i) out[i] = ms[i];
+    return PB_OK;
+}
+
+// what a stage's free function does before it assigns `s->stage = {}`: nullptr entries are skipped
+static inline void search_release(std::initializer_list<void *> dev, void *host, hipEvent_t *ev, int nev)
+{
+    for (void *p : dev)
+        if (p) (void)hipFree(p);
+    if (host) (void)hipHostFree(host);
+    for (int i = 0; i < nev; ++i)
+        if (ev[i]) (void)hipEventDestroy(ev[i]);
+}
+
+SEARCH_LOCAL void search_rfi_free(pb_search *s);
+SEARCH_LOCAL void search_cutouts_free(pb_search *s);
+SEARCH_LOCAL void search_refine_free(pb_search *s);
+SEARCH_LOCAL void search_giants_free(pb_search *s);

@@ -3,7 +3,7 @@
 Stands where the external `heimdall_stream` stands in the reference's chain
 (/root/reference/scripts/start_heimdall_single_antenna:21; candidate line columns
 `S/N, peak_idx, peak_time, tfilt, dmi, dm, ngiant, i0, i1` as parsed by src/candidate.py:8-18).
-The GPU work is libpb_hip.so's pb_search_* (csrc/pb_search.hip); this module only drives it and
+The GPU work is libpb_hip.so's pb_search_* (csrc/search_*.hip); this module only drives it and
 groups the above-threshold samples into candidates on the host.  heimdall is third-party and not in
 the image: its DM spacing, baseline removal and giant merging are not reproduced -- parity with its
 candidate list is unpinned.
@@ -67,8 +67,7 @@ class Searcher(object):
         else:
             rc = self._L.pb_search_create(device, nchan, max_samples, fch1, foff, tsamp, dm_min, dm_max, dm_step,
                                           boxcar_max, zr, len(zap), C.byref(self._s))
-        if rc != 0:
-            raise lp.PbError("pb_search_create failed (%d): %s" % (rc, self._L.pb_search_last_error(None).decode()))
+        self._check(rc, "pb_search_create", handle=False)
         ndm, nbox, md = C.c_int(), C.c_int(), C.c_int()
         self._L.pb_search_info(self._s, C.byref(ndm), C.byref(nbox), C.byref(md))
         self.ndm, self.nbox, self.max_delay = ndm.value, nbox.value, md.value
@@ -80,6 +79,12 @@ class Searcher(object):
         self.dms = dm_min + dm_step * np.arange(self.ndm) if dm_list is None else np.asarray(dm_list, np.float64)
         self._nsamp = 0
         self._tout = 0
+
+    def _check(self, rc, name, exc=None, handle=True):
+        """raise for a non-zero return code: PbError("<name> failed (rc): <last error>"), or exc(<last error>)"""
+        if rc != 0:
+            err = self._L.pb_search_last_error(self._s if handle else None).decode()
+            raise exc(err) if exc else self._lp.PbError("%s failed (%d): %s" % (name, rc, err))
 
     def close(self):
         if getattr(self, "_s", None):
@@ -108,8 +113,7 @@ class Searcher(object):
         """RFI cleaning of every following block before dedispersion (heimdall's narrow and broad stages, this
         project's own definition: include/pb_hip.h, pb_search_set_rfi); set_rfi(False, False) switches it off"""
         rc = self._L.pb_search_set_rfi(self._s, int(bool(narrow)), int(bool(broad)), float(tol), int(boxcar_max))
-        if rc != 0:
-            raise ValueError(self._L.pb_search_last_error(self._s).decode())
+        self._check(rc, None, ValueError)
 
     def rfi_info(self):
         """the last run's cleaning: narrow flags, broad time samples, device ms (0 when it was not cleaned)"""
@@ -121,16 +125,14 @@ class Searcher(object):
         """the last run's channel-major block [nchan][nsamp] u8 as dedispersion read it (cleaned if cleaning was on)"""
         out = np.empty((self.nchan, self._nsamp), np.uint8)
         rc = self._L.pb_search_fetch_clean(self._s, out.ctypes.data_as(C.POINTER(C.c_uint8)), out.nbytes)
-        if rc != 0:
-            raise self._lp.PbError("pb_search_fetch_clean failed (%d): %s" % (rc, self._L.pb_search_last_error(self._s).decode()))
+        self._check(rc, "pb_search_fetch_clean")
         return out
 
     def set_cutouts(self, nsub=64, nt=256, ndmrow=64, max_cands=32):
         """per-candidate cutouts of the last block (include/pb_hip.h, pb_search_set_cutouts): nsub subbands, nt time
         bins, ndmrow DM rows, up to max_cands requests per cutouts() call; max_cands=0 switches them off"""
         rc = self._L.pb_search_set_cutouts(self._s, int(nsub), int(nt), int(ndmrow), int(max_cands))
-        if rc != 0:
-            raise ValueError(self._L.pb_search_last_error(self._s).decode())
+        self._check(rc, None, ValueError)
         self._cut = (int(nsub), int(nt), int(ndmrow), int(max_cands)) if max_cands else None
 
     def cutouts(self, dmi, t, tscr):
@@ -149,8 +151,7 @@ class Searcher(object):
         u32p = C.POINTER(C.c_uint32)
         rc = self._L.pb_search_cutouts(self._s, req.ctypes.data_as(C.POINTER(C.c_int32)), n,
                                        *[out[k].ctypes.data_as(u32p) for k in ("ft", "ft_hits", "dt", "dt_hits")])
-        if rc != 0:
-            raise self._lp.PbError("pb_search_cutouts failed (%d): %s" % (rc, self._L.pb_search_last_error(self._s).decode()))
+        self._check(rc, "pb_search_cutouts")
         rows = req[:, :1].astype(np.int64) - nrow // 2 + np.arange(nrow)[None, :]
         ok = (rows >= 0) & (rows < self.ndm)
         out["dm_rows"] = np.where(ok, np.asarray(self.dms, np.float64)[np.clip(rows, 0, self.ndm - 1)], np.nan)
@@ -169,8 +170,7 @@ class Searcher(object):
         request, a window of half_window samples either side of the peak, the odd widths below wmax, up to max_cands
         requests per refine_raw() call; max_cands=0 switches it off"""
         rc = self._L.pb_search_set_refine(self._s, int(nstep), int(half_window), int(wmax), int(max_cands))
-        if rc != 0:
-            raise ValueError(self._L.pb_search_last_error(self._s).decode())
+        self._check(rc, None, ValueError)
         self._ref = (int(nstep), int(half_window), int(wmax), int(max_cands)) if max_cands else None
 
     def refine_raw(self, t, width, dm_lo, dm_step, want_series=False):
@@ -197,8 +197,7 @@ class Searcher(object):
                                       out["kbest"].ctypes.data_as(i32p), out["opt_sn"].ctypes.data_as(f64p),
                                       out["opt_loc"].ctypes.data_as(i32p),
                                       ser.ctypes.data_as(C.POINTER(C.c_uint32)) if want_series else None)
-        if rc != 0:
-            raise self._lp.PbError("pb_search_refine failed (%d): %s" % (rc, self._L.pb_search_last_error(self._s).decode()))
+        self._check(rc, "pb_search_refine")
         out["widths"] = 2 * np.arange(nw) + 1
         out["dm_lo"], out["dm_step"] = rf[:, 0].astype(np.float64), rf[:, 1].astype(np.float64)
         out["dms"] = rf[:, :1].astype(np.float64) + np.arange(nstep)[None, :] * rf[:, 1:].astype(np.float64)
@@ -260,8 +259,7 @@ class Searcher(object):
         at most sep_time apart make a giant, giants within sep_dm trial DMs, sep_filter in log2 width and sep_time in time
         are linked, up to max_giants giants per giants() call; max_giants=0 switches the stage off"""
         rc = self._L.pb_search_set_giants(self._s, int(sep_time), int(sep_dm), int(sep_filter), int(max_giants))
-        if rc != 0:
-            raise ValueError(self._L.pb_search_last_error(self._s).decode())
+        self._check(rc, None, ValueError)
         self._gi = (int(sep_time), int(sep_dm), int(sep_filter), int(max_giants)) if max_giants else None
 
     def set_planes(self, snr, width_log2):
@@ -273,8 +271,7 @@ class Searcher(object):
             raise ValueError("set_planes: both planes must be [ndm][tout]")
         rc = self._L.pb_search_set_planes(self._s, snr.ctypes.data_as(C.POINTER(C.c_float)),
                                           wl.ctypes.data_as(C.POINTER(C.c_uint8)), snr.shape[1])
-        if rc != 0:
-            raise ValueError(self._L.pb_search_last_error(self._s).decode())
+        self._check(rc, None, ValueError)
         self._tout = snr.shape[1]
 
     def giants(self, thresh, t_lo=0, t_hi=None, want_list=False):
@@ -292,8 +289,7 @@ class Searcher(object):
         buf = np.empty((cap, 8), np.int32)
         rc = self._L.pb_search_giants(self._s, C.c_float(thresh), int(t_lo), int(t_hi), buf.ctypes.data_as(i32p), cap,
                                       C.byref(nc), C.byref(ng), C.byref(ov))
-        if rc != 0:
-            raise self._lp.PbError("pb_search_giants failed (%d): %s" % (rc, self._L.pb_search_last_error(self._s).decode()))
+        self._check(rc, "pb_search_giants")
         b = buf[:nc.value]
         out = dict(snr=b[:, 0].copy().view(np.float32), peak=b[:, 1].copy(), tfilt=b[:, 2].copy(), dmi=b[:, 3].copy(),
                    members=b[:, 4].copy(), npoints=b[:, 5].copy(), i0=b[:, 6].copy(), i1=b[:, 7].copy(),
@@ -302,8 +298,7 @@ class Searcher(object):
             n = C.c_int()
             g = np.empty((0 if ov.value else ng.value, 8), np.int32)
             rc = self._L.pb_search_giant_list(self._s, g.ctypes.data_as(i32p), g.shape[0], C.byref(n))
-            if rc != 0:
-                raise self._lp.PbError("pb_search_giant_list failed (%d): %s" % (rc, self._L.pb_search_last_error(self._s).decode()))
+            self._check(rc, "pb_search_giant_list")
             out["giant_list"] = dict(dmi=g[:, 0].copy(), begin=g[:, 1].copy(), end=g[:, 2].copy(), npts=g[:, 3].copy(),
                                      peak=g[:, 4].copy(), snr=g[:, 5].copy().view(np.float32), tfilt=g[:, 6].copy(),
                                      label=g[:, 7].copy())
@@ -336,8 +331,7 @@ class Searcher(object):
         n, t = C.c_int(), C.c_int()
         rc = self._L.pb_search_peaks(self._s, ptr, on_dev, nsamp, nbit, C.c_float(threshold),
                                      buf.ctypes.data_as(C.POINTER(C.c_int32)), max_out, C.byref(n), C.byref(t))
-        if rc != 0:
-            raise self._lp.PbError("pb_search_peaks failed (%d): %s" % (rc, self._L.pb_search_last_error(self._s).decode()))
+        self._check(rc, "pb_search_peaks")
         self._nsamp = nsamp
         self._tout = t.value
         k = min(n.value, max_out, 1 << 20)        # (the device list holds 2^20 points)
@@ -362,8 +356,7 @@ class Searcher(object):
                                    snr.ctypes.data_as(C.POINTER(C.c_float)), wid.ctypes.data_as(C.POINTER(C.c_uint8)),
                                    series.ctypes.data_as(C.POINTER(C.c_uint32)) if want_series else None,
                                    stats.ctypes.data_as(C.POINTER(C.c_float)), C.byref(t))
-        if rc != 0:
-            raise self._lp.PbError("pb_search_run failed (%d): %s" % (rc, self._L.pb_search_last_error(self._s).decode()))
+        self._check(rc, "pb_search_run")
         self._nsamp = nsamp
         self._tout = tout
         return dict(snr=snr, width_log2=wid, stats=stats, series=series, tout=tout)
