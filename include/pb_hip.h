@@ -296,7 +296,21 @@ void pb_search_destroy(pb_search *s);
 const char *pb_search_last_error(const pb_search *s);
 int pb_search_info(const pb_search *s, int *ndm, int *nbox, int *max_delay);
 /* outputs (host; any may be NULL): snr / width_log2 / series are [ndm][tout], tout = nsamp - max_delay;
- * stats is [ndm][2] = level and rms of each dedispersed series (defined under pb_search_set_baseline below) */
+ * stats is [ndm][2] = level and rms of each dedispersed series (defined under pb_search_set_baseline below).
+ * codes_on_device (pb_search_run and pb_search_peaks alike): 0 = `codes` is host memory and is copied to the device
+ * first; 1 = `codes` is a device address on the search's device (e.g. pb_output_dev's, or a coadder's code buffer) and
+ * is read where it lies, nsamp * nchan * nbit / 8 bytes from `codes` on, by the unpacking transpose and by nothing
+ * after it.  The contract of 1:
+ *   - The search runs on a non-blocking stream of its own, which waits for no other stream, the null stream
+ *     included: whatever produced the bytes must have finished before the call -- the caller synchronises the
+ *     producer's stream (pb_sync for a pb_handle, a stream or device synchronise for anything else).  The search
+ *     queues no wait of its own.
+ *   - The address needs no alignment: the transpose reads single bytes, so a block may start at any byte (any time
+ *     sample of a longer buffer; with 4 or 2 bits the first sample is the low bits of the first byte).
+ *   - The bytes must stay valid and unchanged until the call returns.  Both entry points synchronise the search's stream
+ *     before they return, so the caller may overwrite or free the buffer afterwards; the later stages (cutouts,
+ *     refinement, giants, pb_search_fetch_clean) act on the search's own channel-major copy, not on `codes`.
+ * The results do not depend on codes_on_device (tests/test_gpu_chain.py). */
 int pb_search_run(pb_search *s, const void *codes, int codes_on_device, int nsamp, int nbit, float *snr,
                   uint8_t *width_log2, uint32_t *series, float *stats, int *tout);
 /* Running baseline: the mean over `window_samples` samples around each sample is removed from every

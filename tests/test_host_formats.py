@@ -90,6 +90,29 @@ def test_sigproc_header_bytes():
     assert d["src_raj"] == float(f(int(hh) * 1e4 + int(mm) * 1e2 + float(ss)))
 
 
+def test_search_constants_are_the_sigproc_header_of_the_4096_channel_stream(oracle):
+    """The search's default band and sample time (search.FCH1 / FOFF / TSAMP: what a Searcher fed device codes uses,
+    where there is no file header to read) against the header process_baseband.py writes for the same stream
+    (src/process_baseband.cu:261-266), and the sense of the band against the injected pulse's own delays."""
+    search = importlib.import_module("vlite-fast_amd.search")
+    d, _ = sigproc.read_header(sigproc.sigproc_header(station_id=7, ra=0.87180, dec=-0.72452, name="B0833-45",
+                                                      dmjd=57570.5, npol=1, nbit=8))
+    assert d["nchans"] == 4096 == sigproc.CHANMAX - sigproc.CHANMIN + 1
+    assert d["fch1"] == search.FCH1 and d["foff"] == search.FOFF          # the same binary64, not merely close
+    assert d["tsamp"] == search.TSAMP
+    assert d["foff"] < 0                                                   # channel 0 is the top of the band
+    # foff < 0: the frequency falls with the channel index, so the reference's pulse arrives later and later along
+    # the FFT bins, of which the stream's channel c is bin 2155 + c (src/pb_kernels.cu:338-352)
+    delays = oracle.set_frb_delays(80.0, 1024)
+    assert delays[0] == 0 and np.all(np.diff(delays.astype(np.float64)) > 0)
+    band = delays[sigproc.CHANMIN:sigproc.CHANMAX + 1].astype(np.float64)
+    # and by as much as the search's own delay formula says for these constants (4.15e-3 there, 4.148808e-3 here:
+    # 3e-4 apart; the pulse's bin b sits at 384 - 64 b / 6251 MHz, half a channel below channel b - 2155's centre)
+    f = search.FCH1 + search.FOFF * (np.arange(4096) + 0.5)
+    rows = 4.148808e3 * 80.0 * (f ** -2 - 384.0 ** -2) / (search.TSAMP / 8)
+    assert np.allclose(band, rows, rtol=5e-4, atol=0.01)
+
+
 def test_file_names():
     t = 1467334800   # 2016-07-01 01:00:00 UTC
     fb, fbk, co, cok = sigproc.fb_names(t, 7, "/mnt/ssd/fildata")

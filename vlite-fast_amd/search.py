@@ -326,6 +326,9 @@ class Searcher(object):
             nsamp = codes.size * (8 // nbit) // self.nchan
             ptr, on_dev = codes.ctypes.data_as(C.c_void_p), 0
         else:
+            if nsamp is None:
+                raise ValueError("device_ptr needs nsamp")
+            nsamp = int(nsamp)
             ptr, on_dev = C.c_void_p(device_ptr), 1
         buf = np.empty((max_out, 4), np.int32)
         n, t = C.c_int(), C.c_int()
@@ -339,11 +342,20 @@ class Searcher(object):
         return dict(dmi=b[:, 0].copy(), t=b[:, 1].copy(), snr=b[:, 2].copy().view(np.float32), width_log2=b[:, 3].astype(np.uint8),
                     total=n.value, tout=t.value)
 
-    def run(self, codes, nbit=8, want_series=False):
-        """codes: uint8 array holding nsamp x nchan samples of nbit bits (SIGPROC order).
+    def run(self, codes, nbit=8, want_series=False, device_ptr=None, nsamp=None):
+        """codes: uint8 array holding nsamp x nchan samples of nbit bits (SIGPROC order), or device_ptr + nsamp for
+        codes that are already on the GPU (e.g. PbHandle.output_dev; the contract is under pb_search_run in
+        include/pb_hip.h: the producer's stream synchronised, any byte address, valid until this returns).
         Returns dict(snr [ndm][tout] f32, width_log2 [ndm][tout] u8, stats [ndm][2], series?)."""
-        codes = np.ascontiguousarray(codes, np.uint8).ravel()
-        nsamp = codes.size * (8 // nbit) // self.nchan
+        if device_ptr is None:
+            codes = np.ascontiguousarray(codes, np.uint8).ravel()
+            nsamp = codes.size * (8 // nbit) // self.nchan
+            ptr, on_dev = codes.ctypes.data_as(C.c_void_p), 0
+        else:
+            if nsamp is None:
+                raise ValueError("device_ptr needs nsamp")
+            nsamp = int(nsamp)
+            ptr, on_dev = C.c_void_p(device_ptr), 1
         tout = nsamp - self.max_delay
         if tout < 64:
             raise ValueError("block shorter than the largest dispersion delay (%d samples)" % self.max_delay)
@@ -352,7 +364,7 @@ class Searcher(object):
         stats = np.empty((self.ndm, 2), np.float32)
         series = np.empty((self.ndm, tout), np.uint32) if want_series else None
         t = C.c_int()
-        rc = self._L.pb_search_run(self._s, codes.ctypes.data_as(C.c_void_p), 0, nsamp, nbit,
+        rc = self._L.pb_search_run(self._s, ptr, on_dev, nsamp, nbit,
                                    snr.ctypes.data_as(C.POINTER(C.c_float)), wid.ctypes.data_as(C.POINTER(C.c_uint8)),
                                    series.ctypes.data_as(C.POINTER(C.c_uint32)) if want_series else None,
                                    stats.ctypes.data_as(C.POINTER(C.c_float)), C.byref(t))
