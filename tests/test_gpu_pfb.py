@@ -207,11 +207,12 @@ def _oracle_pfb_chain_mode2(oracle, data, Rr):
     return np.concatenate(codes_raw), np.concatenate(codes_kur), w, flags
 
 
-def _run_pipelined(lp, batches, Rr, rfi_mode, nsets, resident=False):
+def _run_pipelined(lp, batches, Rr, rfi_mode, nsets, resident=False, nbit=8, npol=1, bandpass=None):
     """bench.py's order of calls: batch k goes to buffer set k mod nsets (re-staged every time), its bytes are
     collected nsets - 1 batches later.  resident (needs len(batches) <= nsets): every batch is staged into its set
     and the device is idle before the first pb_process, then the batches are processed back to back with no staging
-    between them -- bench.py's HBM-resident input: nothing but the library's own events orders the kernels."""
+    between them -- bench.py's HBM-resident input: nothing but the library's own events orders the kernels.
+    bandpass: a list that receives get_bandpass(0) after the last batch."""
     S = batches[0].shape[0]
     raw, kur, wts = [], [], []
 
@@ -222,7 +223,7 @@ def _run_pipelined(lp, batches, Rr, rfi_mode, nsets, resident=False):
         kur.append(o["kur"])
         wts.append(o["weights"])
 
-    with lp.PbHandle(nbit=8, rfi_mode=rfi_mode, taps=4, rows_per_seg=Rr, max_seg=S, nsets=nsets) as h:
+    with lp.PbHandle(nbit=nbit, npol=npol, rfi_mode=rfi_mode, taps=4, rows_per_seg=Rr, max_seg=S, nsets=nsets) as h:
         if resident:
             assert len(batches) <= nsets
             for k, d in enumerate(batches):
@@ -240,6 +241,8 @@ def _run_pipelined(lp, batches, Rr, rfi_mode, nsets, resident=False):
                 collect(h, k - (nsets - 1))
         for j in range(max(0, len(batches) - (nsets - 1)), len(batches)):
             collect(h, j)
+        if bandpass is not None:
+            bandpass.append(h.get_bandpass(0))
     return raw, kur, wts
 
 
@@ -326,9 +329,11 @@ def test_pfb_fullsize_two_segments_mode2_bit_exact(oracle):
     assert np.array_equal(kur[0], ref_kur), "excised-stream codes differ"
 
 
-def _run_many(lp, data, Rr, S, rfi_mode, nant, nsets=2):
+def _run_many(lp, data, Rr, S, rfi_mode, nant, nsets=2, nbit=8, bandpass=None, after_batch=None):
     """batches of S segments through one handle of `nant` antennas (antenna a gets the data rolled by a segments):
-    -> (raw, kur, weights) per antenna, concatenated over the batches"""
+    -> (raw, kur, weights) per antenna, concatenated over the batches.  bandpass: a list that receives every antenna's
+    get_bandpass after the last batch; after_batch(h, k) is called once batch k has been queued (and, with more than
+    one buffer set, batch k - nsets + 1 collected)."""
     nb = data.shape[0] // S
     out = [([], [], []) for _ in range(nant)]
 
@@ -341,7 +346,7 @@ def _run_many(lp, data, Rr, S, rfi_mode, nant, nsets=2):
             out[a][1].append(o["kur"])
             out[a][2].append(o["weights"])
 
-    with lp.PbHandle(nant=nant, nbit=8, rfi_mode=rfi_mode, taps=4, rows_per_seg=Rr, max_seg=S, nsets=nsets) as h:
+    with lp.PbHandle(nant=nant, nbit=nbit, rfi_mode=rfi_mode, taps=4, rows_per_seg=Rr, max_seg=S, nsets=nsets) as h:
         for k in range(nb):
             h.select_set(k % nsets)
             for a in range(nant):
@@ -351,8 +356,12 @@ def _run_many(lp, data, Rr, S, rfi_mode, nant, nsets=2):
             h.process(S)
             if k >= nsets - 1:
                 collect(h, k - (nsets - 1))
+            if after_batch is not None:
+                after_batch(h, k)
         for j in range(max(0, nb - (nsets - 1)), nb):
             collect(h, j)
+        if bandpass is not None:
+            bandpass.extend(h.get_bandpass(a) for a in range(nant))
     return [tuple(np.concatenate(x) if x else None for x in o) for o in out]
 
 
@@ -361,7 +370,8 @@ def test_pfb_buffer_set_counts_agree(Rr, S, nb, rfi_mode, nant):
     """The same batches through one, two and three buffer sets (no pipelining; detect beside the next channeliser;
     the kurtosis pass beside the previous channeliser as well) give the same bytes and weights: RFI mode 1 (no raw
     transform), two antennas in one handle, a row count that is no multiple of 32 (8-row detect chunks), rows with
-    code 0 (dropped frames).  The one-set results are the ones the tests above pin to the oracle."""
+    code 0 (dropped frames).  This test only compares the library with itself; the same shapes, modes and antennas
+    are held to the composed oracle, bit for bit, in tests/test_gpu_pfb_matrix.py (test_shapes_and_antennas)."""
     lp = libpb()
     data = make_input(66, Rr, S * nb)
     got = {n: _run_many(lp, data, Rr, S, rfi_mode, nant, nsets=n) for n in (1, 2, 3)}

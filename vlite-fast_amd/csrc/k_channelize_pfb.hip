@@ -10,8 +10,13 @@
 // contributing row before the window is applied; the row weight generalises apply_kurtosis'
 // "fraction of unflagged samples" to the window's energy:
 //     w(g) = sum_{j,b unflagged and present} E[j][b] / sum_{j,b} E[j][b],  E[j][b] = sum_{m in b} taps[j][m]^2.
-// Parity: spectra vs polyphase_filterbank golden (tests, 2e-6), whole chain vs the oracle's kernels
-// composed around the same fp32 FIR (bit-exact, RFI mode 0); the weight definition has no reference.
+// Parity: spectra vs polyphase_filterbank golden (tests, 2e-6); the whole chain bit-exact vs the oracle's kernels
+// composed around the same fp32 FIR (tests/pfb_ref.py, held to float64 restatements of the spectra and of the weights
+// by tests/test_pfb_ref_cpu.py): codes of both streams, weights and the final bandpass state in RFI modes 0/1/2, one
+// and two output pols, 8/4/2 bits, two antennas per handle, pb_reset_history of one antenna in either history slot,
+// calls of nseg < max_seg, a stream that starts with code 0, zero codes in carried rows, inject_now > 0
+// (tests/test_gpu_pfb_matrix.py), pipelined sets and R = 1024 (tests/test_gpu_pfb.py).  The weight definition itself
+// has no counterpart in the reference.
 // ordinary (L2-allocating) stores of the power planes here: with non-temporal ones this kernel is 6 % faster alone
 // (0.68 against 0.73 ms per launch) and the pipeline 3 % slower (1.02 against 0.995 ms per step: detect's reads of
 // the planes then come from further away), and the step is what counts (profiles/r03_notes.md)
