@@ -529,6 +529,61 @@ int pb_search_set_planes(pb_search *s, const float *snr, const uint8_t *width_lo
  * and of everything with the copy to the host; *nsweeps (may be NULL) = hook / jump sweeps of the labelling */
 int pb_search_giant_timers(const pb_search *s, float *ms3, int *nsweeps);
 
+/* Streaming: a gulp accumulated on the device from pieces of any length, and its dispersion tail handed on without
+ * leaving the device.  In production the search stands behind the filterbank, which leaves one second of code bytes in
+ * device memory at a time; heimdall gathers 30720 samples into a gulp and searches it together with the end of the
+ * stream before it.  Off until pb_search_set_gulp; a pb_search on which it was never called allocates nothing more,
+ * launches nothing more and gives the results it gave before.
+ * The accumulated block IS the search's channel-major block xt[c][t] (u8, c in [0, nchan), pitch >= max_samples), the
+ * one that pb_search_run / pb_search_peaks fill with their transpose; `fill` counts the samples per channel that it
+ * holds.  Every entry below returns PB_EINVAL with a message (pb_search_last_error) and changes nothing when the stage
+ * is off, when there is no handle ("no search handle"), or in the cases named with it.
+ *   pb_search_set_gulp(s, keep_max)  switches the stage on with an empty block (fill = 0) and allocates the side buffer
+ *           of nchan x keep_max bytes; keep_max = the most samples that pb_search_gulp_advance may hand on.  0 switches
+ *           the stage off and frees the buffer.  Refused: keep_max < 0 or > max_samples.
+ *   pb_search_push(s, codes, codes_on_device, nsamp, nbit, &fill)  appends nsamp samples in SIGPROC order
+ *           [time][nchan], nbit in {8, 4, 2}, low bits first within a byte -- what pb_search_run accepts --:
+ *           xt[c][fill + t] = sample (t, c) for t in [0, nsamp), then fill += nsamp; *fill (may be NULL) = the new fill.
+ *           codes_on_device = 0: host bytes, staged through the buffer that pb_search_run stages its host blocks
+ *           through.  1: device bytes read where they lie, under the contract of pb_search_run: the producer synchronised
+ *           by the caller, any byte address, nothing read outside [codes, codes + nsamp * nchan * nbit / 8).  The call
+ *           returns when the bytes have been consumed.  Successive pushes may differ in nbit and in where their bytes
+ *           lie.  A source whose address and row length nchan * nbit / 8 are multiples of 16 bytes (pb_output_dev, a
+ *           coadder's code buffer, the staging buffer) is read with 16-byte loads, any other byte by byte; the result
+ *           is the same.  nsamp = 0 appends nothing.  Refused, appending nothing: a bad nbit; fill + nsamp >
+ *           max_samples; nsamp * nchan * nbit not a multiple of 8 (a piece ends on a byte); a push onto a block that a
+ *           gulp call has cleaned in place (see below: advance first).
+ *   pb_search_gulp_peaks(s, threshold, peaks, max_out, &npeaks, &tout), pb_search_gulp_run(s, snr, width_log2, series,
+ *           stats, &tout)  what pb_search_peaks / pb_search_run do on a block of nsamp = fill samples, from the RFI
+ *           cleaning on (the same kernels), with the same outputs and the same refusals, fill - max_delay < 64 among
+ *           them.  Afterwards cutouts, refinement, giants, pb_search_fetch_clean and pb_search_timers (its first two
+ *           entries: nothing, and putting the raw tail aside) behave as after pb_search_peaks, block coordinates being
+ *           positions in the accumulated block.  fill is unchanged, and a second call without a push in between returns
+ *           the same bytes.  With cleaning on (pb_search_set_rfi) the block is cleaned in place, once: the raw samples
+ *           [fill - min(keep_max, fill), fill) are first copied to the side buffer, a second call reads the block as the
+ *           first one left it (the cleaning and its counts are the first call's; a pb_search_set_rfi in between takes
+ *           effect after the next advance), and until pb_search_gulp_advance the raw block no longer exists:
+ *           pb_search_push and pb_search_gulp_fetch are refused.
+ *   pb_search_gulp_advance(s, keep)  the raw samples [fill - keep, fill) of every channel -- as pushed, not as cleaned --
+ *           become the samples [0, keep), and fill = keep.  Refused: keep < 0, keep > fill, keep > keep_max.  Device
+ *           copies only; where source and destination overlap (keep > fill - keep) or the block was cleaned, the samples
+ *           go through the side buffer, so the move is exact whatever order a copy works in.
+ *   pb_search_gulp_fetch(s, xt, nbytes, &fill)  the raw accumulated block [nchan][fill] -> host (tests, debugging a
+ *           host); nbytes >= nchan * fill.
+ *   pb_search_gulp_timers(s, ms3)  device time in ms of the last push's copy to the device (0 for device bytes) and
+ *           append, and of the last advance.
+ * pb_search_run / pb_search_peaks on a handle with the stage on overwrite the block as they always did, give their usual
+ * results, and leave the stage empty (fill = 0).
+ * tests/test_gpu_search_stream.py: the block equals the unpacked concatenation of the pieces however they are cut,
+ * packed and placed, and a stream fed in pieces gives the candidates of the same stream searched in whole host gulps. */
+int pb_search_set_gulp(pb_search *s, int keep_max);
+int pb_search_push(pb_search *s, const void *codes, int codes_on_device, int nsamp, int nbit, int *fill);
+int pb_search_gulp_peaks(pb_search *s, float threshold, int32_t *peaks, int max_out, int *npeaks, int *tout);
+int pb_search_gulp_run(pb_search *s, float *snr, uint8_t *width_log2, uint32_t *series, float *stats, int *tout);
+int pb_search_gulp_advance(pb_search *s, int keep);
+int pb_search_gulp_fetch(pb_search *s, uint8_t *xt, size_t nbytes, int *fill);
+int pb_search_gulp_timers(const pb_search *s, float *ms3);
+
 /* Page-locked host memory for the blocks handed to pb_submit_vdif(_at) (H2D copies from pageable memory are
  * staged and synchronous); the reference allocates its 1-s host buffer the same way (cudaMallocHost,
  * src/process_baseband.cu:579).  A host program above this ABI needs no HIP headers.  NULL on failure. */

@@ -1,6 +1,6 @@
 // What the search's translation units share on the host side: the handle, the dispersion delay, the error and timer
 // helpers, and each stage's free function.  search_run.hip holds the core (create .. fetch_clean) and the RFI cleaning;
-// search_cutout.hip, search_refine.hip and search_giants.hip one optional stage each, kernels and host side together (a
+// search_cutout.hip, search_refine.hip, search_giants.hip and search_stream.hip one optional stage each, kernels and host side together (a
 // kernel lives in the file that launches it).  Device-only helpers: search_dev.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -99,6 +99,17 @@ struct pb_search {
         hipEvent_t ev[4] = {};             // start, giants written, candidates made, copy done
         float ms[3] = {};                  // last call: giant pass, labelling + merge, everything with the copy
     } gi;
+    // streaming (pb_search_set_gulp): d_xt is filled piece by piece; the side buffer exists while it is switched on (keep_max > 0)
+    struct {
+        int keep_max = 0;
+        int fill = 0;                      // samples per channel accumulated in d_xt
+        int cleaned = 0;                   // d_xt[.][0, fill) was cleaned in place by a gulp call since the last push / advance
+        int tail_n = 0;                    // d_tail row c holds the raw samples [fill - tail_n, fill) of channel c
+        uint8_t *d_tail = nullptr;         // [nchan][kpitch]
+        size_t kpitch = 0;
+        hipEvent_t ev[5] = {};             // push: start, bytes on the device, appended; advance: start, end
+        float ms[3] = {};                  // last push: copy, append; last advance
+    } gp;
 };
 
 // The dispersion delay of one channel in samples, in double: 4.148808e3 MHz^2 s (src/candidate.py:33) x DM x
@@ -168,3 +179,11 @@ SEARCH_LOCAL void search_rfi_free(pb_search *s);
 SEARCH_LOCAL void search_cutouts_free(pb_search *s);
 SEARCH_LOCAL void search_refine_free(pb_search *s);
 SEARCH_LOCAL void search_giants_free(pb_search *s);
+SEARCH_LOCAL void search_gulp_free(pb_search *s);
+
+// search_run.hip, for search_stream.hip: the search from the cleaning on over the nsamp samples that d_xt holds (after
+// ev[2]; `cleaned`: leave the cleaning out, the block is cleaned already), and the copies to the host that end
+// pb_search_run / pb_search_peaks
+SEARCH_LOCAL int search_block(pb_search *s, int nsamp, float thresh, bool want_peaks, bool cleaned);
+SEARCH_LOCAL int search_run_out(pb_search *s, float *snr, uint8_t *width_log2, uint32_t *series, float *stats, int *tout_out);
+SEARCH_LOCAL int search_peaks_out(pb_search *s, int32_t *peaks, int max_out, int *npeaks, int *tout_out);

@@ -18,7 +18,8 @@
 // k_series_stats / k_boxcar, k_rfi_broad_list (the flagged samples) and k_rfi_broad_mask (those samples -> median).
 // The optional stages that act on what a run leaves on the device have a file each, kernels and host side together:
 // per-candidate cutouts (search_cutout.hip), a candidate's DM, width and S/N refined on a fine DM grid
-// (search_refine.hip), giants and clusters of giants (search_giants.hip).  This file is the core -- create .. destroy,
+// (search_refine.hip), giants and clusters of giants (search_giants.hip).  The streaming stage (search_stream.hip)
+// stands before the cleaning instead: it fills the channel-major block piece by piece and enters at search_block.  This file is the core -- create .. destroy,
 // run / peaks, the kernels of steps 1-3 -- and the cleaning, which launches k_dedisperse .. k_boxcar for its zero-DM
 // series.  The handle and the host helpers: search_internal.h; the device helpers: search_dev.h.
 #include "search_internal.h"
@@ -575,6 +576,7 @@ extern "C" void pb_search_destroy(pb_search *s)
     search_cutouts_free(s);
     search_refine_free(s);
     search_giants_free(s);
+    search_gulp_free(s);
     search_release({s->d_codes, s->d_xt, s->d_delay, s->d_D, s->d_stats, s->d_snr, s->d_wid, s->d_P, s->d_peaks, s->d_chans},
                    nullptr, s->ev, 7);
     if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -653,28 +655,17 @@ static int search_clean(pb_search *s, int nsamp)
     return PB_OK;
 }
 
-static int search_run(pb_search *s, const void *codes, int codes_on_device, int nsamp, int nbit, float thresh,
-                      bool want_peaks)
+// From the channel-major block on: d_xt holds nsamp samples per channel and ev[2] has been recorded.  The cleaning (in
+// place; `cleaned`: the block has been cleaned already and is read as it lies), dedispersion, prefix sums and
+// statistics, boxcars.  What pb_search_run / pb_search_peaks run after their transpose, and pb_search_gulp_run /
+// pb_search_gulp_peaks (search_stream.hip) on the accumulated block.
+int search_block(pb_search *s, int nsamp, float thresh, bool want_peaks, bool cleaned)
 {
-    if (!s || !codes) return PB_EINVAL;
-    if (nsamp > s->max_samples || !(nbit == 8 || nbit == 4 || nbit == 2))
-        return search_fail(s, "pb_search_run", "block too long or bad nbit");
     const int tout = nsamp - s->max_delay;
-    if (tout < 64) return search_fail(s, "pb_search_run", "block shorter than the largest dispersion delay");
-    SCHK(s, hipSetDevice(s->device));
-    const size_t nbytes = (size_t)nsamp * s->nchan * nbit / 8;
-    const uint8_t *d_codes = (const uint8_t *)codes;
-    SCHK(s, hipEventRecord(s->ev[0], s->stream));
-    if (!codes_on_device) {
-        SCHK(s, hipMemcpyAsync(s->d_codes, codes, nbytes, hipMemcpyHostToDevice, s->stream));
-        d_codes = s->d_codes;
-    }
-    SCHK(s, hipEventRecord(s->ev[1], s->stream));
-    dim3 gt((nsamp + 63) / 64, (s->nchan + 63) / 64);
-    k_transpose_codes<<<gt, 256, 0, s->stream>>>(d_codes, s->d_xt, nsamp, s->nchan, nbit, s->tpitch);
-    SCHK(s, hipEventRecord(s->ev[2], s->stream));
     s->rfi.ran = s->rfi.narrow || s->rfi.broad;
-    if (s->rfi.ran) {
+    if (s->rfi.ran && cleaned) {
+        SCHK(s, hipEventRecord(s->rfi.ev[0], s->stream));
+    } else if (s->rfi.ran) {
         const int rc = search_clean(s, nsamp);
         if (rc) return rc;
     }
@@ -697,6 +688,32 @@ static int search_run(pb_search *s, const void *codes, int codes_on_device, int 
     return PB_OK;
 }
 
+static int search_run(pb_search *s, const void *codes, int codes_on_device, int nsamp, int nbit, float thresh,
+                      bool want_peaks)
+{
+    if (!s || !codes) return PB_EINVAL;
+    if (nsamp > s->max_samples || !(nbit == 8 || nbit == 4 || nbit == 2))
+        return search_fail(s, "pb_search_run", "block too long or bad nbit");
+    const int tout = nsamp - s->max_delay;
+    if (tout < 64) return search_fail(s, "pb_search_run", "block shorter than the largest dispersion delay");
+    SCHK(s, hipSetDevice(s->device));
+    const size_t nbytes = (size_t)nsamp * s->nchan * nbit / 8;
+    const uint8_t *d_codes = (const uint8_t *)codes;
+    s->gp.fill = 0;                                     // the transpose overwrites the accumulated block of the gulp stage
+    s->gp.cleaned = 0;
+    s->gp.tail_n = 0;
+    SCHK(s, hipEventRecord(s->ev[0], s->stream));
+    if (!codes_on_device) {
+        SCHK(s, hipMemcpyAsync(s->d_codes, codes, nbytes, hipMemcpyHostToDevice, s->stream));
+        d_codes = s->d_codes;
+    }
+    SCHK(s, hipEventRecord(s->ev[1], s->stream));
+    dim3 gt((nsamp + 63) / 64, (s->nchan + 63) / 64);
+    k_transpose_codes<<<gt, 256, 0, s->stream>>>(d_codes, s->d_xt, nsamp, s->nchan, nbit, s->tpitch);
+    SCHK(s, hipEventRecord(s->ev[2], s->stream));
+    return search_block(s, nsamp, thresh, want_peaks, false);
+}
+
 // after the run's last event: stage times, and the cleaning's time and counts (the dedispersion stage starts where
 // the cleaning ends)
 static int search_times(pb_search *s)
@@ -715,14 +732,9 @@ static int search_times(pb_search *s)
     return PB_OK;
 }
 
-// codes: nsamp x nchan samples of nbit bits in SIGPROC order (host, or device if codes_on_device).
-// Outputs (host, any may be NULL): snr [ndm][tout] float, width_log2 [ndm][tout] u8,
-// series [ndm][tout] u32 (the dedispersed sums), stats [ndm][2]; tout = nsamp - max_delay.
-extern "C" int pb_search_run(pb_search *s, const void *codes, int codes_on_device, int nsamp, int nbit, float *snr,
-                             uint8_t *width_log2, uint32_t *series, float *stats, int *tout_out)
+// the planes, series and statistics of the run that was just queued -> host, then the stage times
+int search_run_out(pb_search *s, float *snr, uint8_t *width_log2, uint32_t *series, float *stats, int *tout_out)
 {
-    int rc = search_run(s, codes, codes_on_device, nsamp, nbit, 0.f, false);
-    if (rc) return rc;
     const int tout = s->last_tout;
     SCHK(s, hipStreamSynchronize(s->stream));
     if (snr) SCHK(s, hipMemcpy2D(snr, tout * sizeof(float), s->d_snr, s->tpitch * sizeof(float), tout * sizeof(float), s->ndm, hipMemcpyDeviceToHost));
@@ -731,10 +743,37 @@ extern "C" int pb_search_run(pb_search *s, const void *codes, int codes_on_devic
     if (stats) SCHK(s, hipMemcpy(stats, s->d_stats, (size_t)s->ndm * 2 * sizeof(float), hipMemcpyDeviceToHost));
     SCHK(s, hipEventRecord(s->ev[6], s->stream));
     SCHK(s, hipEventSynchronize(s->ev[6]));
-    rc = search_times(s);
+    const int rc = search_times(s);
     if (rc) return rc;
     if (tout_out) *tout_out = tout;
     return PB_OK;
+}
+
+// the peak list of the run that was just queued -> host, then the stage times
+int search_peaks_out(pb_search *s, int32_t *peaks, int max_out, int *npeaks, int *tout_out)
+{
+    int32_t n = 0;
+    SCHK(s, hipMemcpyAsync(&n, s->d_peaks, sizeof n, hipMemcpyDeviceToHost, s->stream));
+    SCHK(s, hipStreamSynchronize(s->stream));
+    const int ncopy = std::min(std::min((int)n, max_out), s->max_peaks);      // never past the device list
+    if (ncopy > 0) SCHK(s, hipMemcpy(peaks, s->d_peaks + 1, (size_t)ncopy * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    SCHK(s, hipEventRecord(s->ev[6], s->stream));
+    SCHK(s, hipEventSynchronize(s->ev[6]));
+    const int rc = search_times(s);
+    if (rc) return rc;
+    *npeaks = n;
+    if (tout_out) *tout_out = s->last_tout;
+    return PB_OK;
+}
+
+// codes: nsamp x nchan samples of nbit bits in SIGPROC order (host, or device if codes_on_device).
+// Outputs (host, any may be NULL): snr [ndm][tout] float, width_log2 [ndm][tout] u8,
+// series [ndm][tout] u32 (the dedispersed sums), stats [ndm][2]; tout = nsamp - max_delay.
+extern "C" int pb_search_run(pb_search *s, const void *codes, int codes_on_device, int nsamp, int nbit, float *snr,
+                             uint8_t *width_log2, uint32_t *series, float *stats, int *tout_out)
+{
+    const int rc = search_run(s, codes, codes_on_device, nsamp, nbit, 0.f, false);
+    return rc ? rc : search_run_out(s, snr, width_log2, series, stats, tout_out);
 }
 
 // The search as the production chain uses it: only the (DM, sample) points at or above `threshold` come back
@@ -745,20 +784,8 @@ extern "C" int pb_search_peaks(pb_search *s, const void *codes, int codes_on_dev
                                float threshold, int32_t *peaks, int max_out, int *npeaks, int *tout_out)
 {
     if (!peaks || !npeaks || max_out < 1) return PB_EINVAL;
-    int rc = search_run(s, codes, codes_on_device, nsamp, nbit, threshold, true);
-    if (rc) return rc;
-    int32_t n = 0;
-    SCHK(s, hipMemcpyAsync(&n, s->d_peaks, sizeof n, hipMemcpyDeviceToHost, s->stream));
-    SCHK(s, hipStreamSynchronize(s->stream));
-    const int ncopy = std::min(std::min((int)n, max_out), s->max_peaks);      // never past the device list
-    if (ncopy > 0) SCHK(s, hipMemcpy(peaks, s->d_peaks + 1, (size_t)ncopy * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
-    SCHK(s, hipEventRecord(s->ev[6], s->stream));
-    SCHK(s, hipEventSynchronize(s->ev[6]));
-    rc = search_times(s);
-    if (rc) return rc;
-    *npeaks = n;
-    if (tout_out) *tout_out = s->last_tout;
-    return PB_OK;
+    const int rc = search_run(s, codes, codes_on_device, nsamp, nbit, threshold, true);
+    return rc ? rc : search_peaks_out(s, peaks, max_out, npeaks, tout_out);
 }
 
 extern "C" int pb_search_timers(const pb_search *s, float *ms6)

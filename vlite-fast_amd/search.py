@@ -72,6 +72,7 @@ class Searcher(object):
         self._L.pb_search_info(self._s, C.byref(ndm), C.byref(nbox), C.byref(md))
         self.ndm, self.nbox, self.max_delay = ndm.value, nbox.value, md.value
         self.nchan, self.tsamp = nchan, tsamp
+        self.max_samples = max_samples
         self.fch1, self.foff = fch1, foff
         self._cut = None                 # (nsub, nt, ndmrow, max_cands) once set_cutouts has switched them on
         self._ref = None                 # (nstep, half_window, wmax, max_cands) once set_refine has switched it on
@@ -342,6 +343,92 @@ class Searcher(object):
         return dict(dmi=b[:, 0].copy(), t=b[:, 1].copy(), snr=b[:, 2].copy().view(np.float32), width_log2=b[:, 3].astype(np.uint8),
                     total=n.value, tout=t.value)
 
+    def set_gulp(self, keep_max):
+        """streaming (include/pb_hip.h, pb_search_set_gulp): pieces pushed with push() accumulate in the search's block on
+        the device, gulp_peaks() / gulp_run() search what has accumulated, gulp_advance(keep) hands its last keep <=
+        keep_max samples on to the next gulp without leaving the device; keep_max=0 switches the stage off"""
+        rc = self._L.pb_search_set_gulp(self._s, int(keep_max))
+        self._check(rc, None, ValueError)
+
+    def _codes_arg(self, codes, nbit, device_ptr, nsamp):
+        """(pointer, codes_on_device, nsamp, what keeps the host bytes alive) of a host array or a device address"""
+        if device_ptr is None:
+            codes = np.ascontiguousarray(codes, np.uint8).ravel()
+            if nsamp is None:
+                nsamp = codes.size * 8 // (nbit * self.nchan) if nbit in (8, 4, 2) else 0
+            elif codes.size * 8 < int(nsamp) * self.nchan * nbit:
+                raise ValueError("codes holds fewer than nsamp samples")
+            return codes.ctypes.data_as(C.c_void_p), 0, int(nsamp), codes
+        if nsamp is None:
+            raise ValueError("device_ptr needs nsamp")
+        return C.c_void_p(device_ptr), 1, int(nsamp), None
+
+    def push(self, codes=None, nbit=8, device_ptr=None, nsamp=None):
+        """append a piece to the accumulated block: a host uint8 array of nsamp x nchan samples of nbit bits (SIGPROC
+        order), or device_ptr + nsamp for bytes that are already on the GPU (the contract of run()).  Returns the
+        block's new length in samples."""
+        ptr, on_dev, nsamp, keep = self._codes_arg(codes, nbit, device_ptr, nsamp)
+        fill = C.c_int()
+        rc = self._L.pb_search_push(self._s, ptr, on_dev, nsamp, int(nbit), C.byref(fill))
+        self._check(rc, "pb_search_push")
+        return fill.value
+
+    def gulp_peaks(self, threshold, max_out=1 << 18):
+        """peaks() on the accumulated block: the same dict"""
+        buf = np.empty((max_out, 4), np.int32)
+        n, t = C.c_int(), C.c_int()
+        rc = self._L.pb_search_gulp_peaks(self._s, C.c_float(threshold), buf.ctypes.data_as(C.POINTER(C.c_int32)), max_out,
+                                          C.byref(n), C.byref(t))
+        self._check(rc, "pb_search_gulp_peaks")
+        self._nsamp = t.value + self.max_delay
+        self._tout = t.value
+        b = buf[:min(n.value, max_out, 1 << 20)]
+        return dict(dmi=b[:, 0].copy(), t=b[:, 1].copy(), snr=b[:, 2].copy().view(np.float32), width_log2=b[:, 3].astype(np.uint8),
+                    total=n.value, tout=t.value)
+
+    def gulp_run(self, want_series=False):
+        """run() on the accumulated block: the same dict"""
+        fill = self.gulp_fill()
+        tout = max(fill - self.max_delay, 1)
+        snr = np.empty((self.ndm, tout), np.float32)
+        wid = np.empty((self.ndm, tout), np.uint8)
+        stats = np.empty((self.ndm, 2), np.float32)
+        series = np.empty((self.ndm, tout), np.uint32) if want_series else None
+        t = C.c_int()
+        rc = self._L.pb_search_gulp_run(self._s, snr.ctypes.data_as(C.POINTER(C.c_float)), wid.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                        series.ctypes.data_as(C.POINTER(C.c_uint32)) if want_series else None,
+                                        stats.ctypes.data_as(C.POINTER(C.c_float)), C.byref(t))
+        self._check(rc, "pb_search_gulp_run")
+        self._nsamp = fill
+        self._tout = t.value
+        return dict(snr=snr, width_log2=wid, stats=stats, series=series, tout=t.value)
+
+    def gulp_fill(self):
+        """samples per channel in the accumulated block"""
+        fill = C.c_int()
+        rc = self._L.pb_search_push(self._s, None, 0, 0, 8, C.byref(fill))
+        self._check(rc, "pb_search_push")
+        return fill.value
+
+    def gulp_advance(self, keep):
+        """the last `keep` raw samples of the accumulated block become its first, the rest is dropped"""
+        rc = self._L.pb_search_gulp_advance(self._s, int(keep))
+        self._check(rc, "pb_search_gulp_advance")
+
+    def gulp_fetch(self):
+        """the raw accumulated block [nchan][fill] u8"""
+        out = np.empty((self.nchan, self.gulp_fill()), np.uint8)
+        fill = C.c_int()
+        rc = self._L.pb_search_gulp_fetch(self._s, out.ctypes.data_as(C.POINTER(C.c_uint8)), out.nbytes, C.byref(fill))
+        self._check(rc, "pb_search_gulp_fetch")
+        return out
+
+    def gulp_timers(self):
+        """device ms of the last push(): copy to the device, append; and of the last gulp_advance()"""
+        t = (C.c_float * 3)()
+        self._L.pb_search_gulp_timers(self._s, t)
+        return dict(copy=float(t[0]), append=float(t[1]), advance=float(t[2]))
+
     def run(self, codes, nbit=8, want_series=False, device_ptr=None, nsamp=None):
         """codes: uint8 array holding nsamp x nchan samples of nbit bits (SIGPROC order), or device_ptr + nsamp for
         codes that are already on the GPU (e.g. PbHandle.output_dev; the contract is under pb_search_run in
@@ -449,6 +536,26 @@ def candidates_from_giants(res, dms, tsamp, sample0=0):
                  npoints=int(res["npoints"][k])) for k in order]
 
 
+def gulp_cuts(since, nsamp, gulp):
+    """Where a piece of nsamp samples is cut when `since` samples (0 <= since < gulp) have accumulated since the last
+    fire and a fire is due every `gulp` new samples: a list of (first sample of the part within the piece, its length,
+    whether a fire follows it).  Every part is non-empty, the parts tile the piece in order, a fire follows exactly the
+    parts that complete a gulp -- so a piece that ends where a gulp ends has its fire and no empty part after it, and an
+    empty piece gives []."""
+    since, nsamp, gulp = int(since), int(nsamp), int(gulp)
+    if gulp < 1 or not 0 <= since < gulp or nsamp < 0:
+        raise ValueError("gulp_cuts: gulp >= 1, 0 <= since < gulp, nsamp >= 0")
+    out, off = [], 0
+    while off < nsamp:
+        k = min(gulp - since, nsamp - off)
+        since += k
+        out.append((off, k, since == gulp))
+        off += k
+        if since == gulp:
+            since = 0
+    return out
+
+
 class GulpSearch(object):
     """The search over a stream of filterbank samples in gulps, as heimdall runs it (-nsamps_gulp 30720,
     scripts/start_heimdall_single_antenna:21): every gulp is searched together with the last
@@ -473,11 +580,24 @@ class GulpSearch(object):
     candidates come from the device's giants and clusters (Searcher.set_giants / giants, candidates_from_giants) instead
     of the point list and group_points; the point list is not pulled at all.  A gulp with more than max_giants giants
     yields no candidates and one log line.  A run of hot samples cut by the end of a gulp's complete samples is two
-    giants, one in each gulp's call."""
+    giants, one in each gulp's call.
+    gulp=N: the stream arrives through feed() in pieces of any length, 8, 4 or 2 bits, host or device memory, and is
+    gathered on the device (Searcher.set_gulp / push): every N new samples the accumulated block is searched as push()
+    searches a block of N new samples, and its last max_delay + widest - 1 raw samples are handed on without leaving the
+    device.  feed(p1) .. feed(pk) + finish() return, in order, the candidates of push(b1) .. push(bm) + finish() over
+    the same stream cut into blocks of N, the remainder last (tests/test_gpu_search_stream.py).  gulp=None (default):
+    push() only."""
 
     def __init__(self, searcher, threshold=6.0, nbit=8, coincidencer=None, utc_start="1970-01-01-00:00:00", beam=1,
-                 cutouts=None, refine=None, giants=None):
+                 cutouts=None, refine=None, giants=None, gulp=None):
         self.s, self.threshold, self.nbit = searcher, threshold, nbit
+        self.gulp = None
+        if gulp is not None:
+            if int(gulp) < 1:
+                raise ValueError("GulpSearch(gulp=...): at least one sample")
+            self.gulp = int(gulp)
+            self.since = 0               # samples fed since the last fire
+            self.early = None            # finish()'s candidates where the latest fire had to make them (_fire)
         self.gi = giants is not None
         if self.gi:
             searcher.set_giants(**giants)
@@ -497,6 +617,9 @@ class GulpSearch(object):
         self.ov = (1 << (searcher.nbox - 1)) - 1        # widest boxcar - 1
         self.pending = None              # peaks of the latest gulp's last `ov` output samples (for finish())
         self.coincidencer, self.utc_start, self.beam = coincidencer, utc_start, beam
+        if self.gulp is not None:
+            searcher.set_gulp(min(searcher.max_delay + self.ov, searcher.max_samples))
+            self.fill = 0
 
     def _send(self, cands, first, nsamps):
         if self.coincidencer:
@@ -554,14 +677,23 @@ class GulpSearch(object):
         if data.shape[0] - self.s.max_delay < 64 + self.ov:
             self.tail = data                          # not enough yet for one output block
             return []
+        cands, first, nout = self._search_block(data, data.shape[0])
+        keep = min(self.s.max_delay + self.ov, data.shape[0])
+        self.tail = data[data.shape[0] - keep:].copy()
+        self._send(cands, first, nout)
+        return cands
+
+    def _search_block(self, data, fill):
+        """push()'s work from the search on: the block is `data` (host, [fill][nchan]) or, with data None, the `fill`
+        samples accumulated on the device.  Returns (candidates, first, nout)."""
         if self.gi:
             # the same entry with a threshold no sample reaches: the block is searched, no point comes back
-            pk = self.s.peaks(data, float("inf"), nbit=8, max_out=1)
+            pk = self.s.peaks(data, float("inf"), nbit=8, max_out=1) if data is not None else self.s.gulp_peaks(float("inf"), max_out=1)
             nout = pk["tout"] - self.ov
             cands = self._giants(0, nout, self.done)
             self.pending = (nout, self.done, pk["tout"])
         else:
-            pk = self.s.peaks(data, self.threshold, nbit=8)
+            pk = self.s.peaks(data, self.threshold, nbit=8) if data is not None else self.s.gulp_peaks(self.threshold)
             nout = pk["tout"] - self.ov                   # samples with every width tried
             full = pk["t"] < nout
             cands = candidates_from_peaks(self._subset(pk, full), self.s.dms, self.s.tsamp, sample0=self.done)
@@ -570,23 +702,81 @@ class GulpSearch(object):
         self._cutouts(cands, first)
         self._refine(cands, first)
         self.done += nout
-        keep = min(self.s.max_delay + self.ov, data.shape[0])
-        self.tail = data[data.shape[0] - keep:].copy()
+        return cands, first, nout
+
+    def _fire(self):
+        """the accumulated block searched as push() searches tail + block, then its tail handed on"""
+        self.since = 0
+        fill = self.fill
+        if fill - self.s.max_delay < 64 + self.ov:
+            return []                                 # not enough yet for one output block: nothing is dropped
+        cands, first, nout = self._search_block(None, fill)
+        # finish() cuts out and refines its candidates from the block of the latest search, which the advance below
+        # and the pieces after it overwrite: where either is asked for, they are made now and kept for finish()
+        self.early = self._pending_cands() if (self.cut or self.ref) else None
         self._send(cands, first, nout)
+        self.s.gulp_advance(min(self.s.max_delay + self.ov, fill))
+        self.fill = min(self.s.max_delay + self.ov, fill)
         return cands
 
+    def feed(self, codes=None, nbit=8, device_ptr=None, nsamp=None):
+        """GulpSearch(gulp=N): a piece of the stream, any number of samples of nbit bits in SIGPROC order -- a host uint8
+        array (packed as in a file), or device_ptr + nsamp for bytes on the GPU (Searcher.run's contract).  Returns the
+        candidates of the gulps that the piece completed (often none)."""
+        if self.gulp is None:
+            raise ValueError("feed() needs GulpSearch(gulp=N)")
+        nchan = self.s.nchan
+        if nbit not in (8, 4, 2) or (nchan * nbit) % 8:
+            raise ValueError("feed: nbit 8, 4 or 2, and a time sample must fill whole bytes (nchan x nbit a multiple of 8)")
+        rowb = nchan * nbit // 8
+        if device_ptr is None:
+            codes = np.ascontiguousarray(codes, np.uint8).ravel()
+            if nsamp is None:
+                nsamp = codes.size // rowb
+            if codes.size < nsamp * rowb:
+                raise ValueError("codes holds fewer than nsamp samples")
+        elif nsamp is None:
+            raise ValueError("device_ptr needs nsamp")
+        out = []
+        for off, n, fire in gulp_cuts(self.since, nsamp, self.gulp):
+            if device_ptr is None:
+                self.fill = self.s.push(codes[off * rowb:(off + n) * rowb], nbit=nbit, nsamp=n)
+            else:
+                self.fill = self.s.push(nbit=nbit, device_ptr=device_ptr + off * rowb, nsamp=n)
+            self.since += n
+            if fire:
+                out += self._fire()
+        return out
+
     def finish(self):
-        """end of the stream: candidates of the last widest - 1 output samples"""
-        if self.pending is None:
-            return []
+        """end of the stream: candidates of the last widest - 1 output samples; with gulp=N first those of the samples
+        fed since the last fire (returned together, the partial gulp's first)"""
+        return self.flush() + self._finish()
+
+    def flush(self):
+        """GulpSearch(gulp=N): search the partial gulp fed since the last fire now (finish() does it first; a caller that
+        wants the two batches apart, each with its own last_first, calls flush() and then finish())"""
+        return self._fire() if self.gulp is not None and self.since > 0 else []
+
+    def _pending_cands(self):
+        """the candidates of the latest search's last widest - 1 output samples, from the block that is still the
+        searcher's current one"""
         pk, sample0, tout = self.pending
-        self.pending = None
         if self.gi:                                # pk: the first sample of the block that push() left out
             cands = self._giants(pk, tout, sample0) if pk < tout else []
         else:
             cands = candidates_from_peaks(pk, self.s.dms, self.s.tsamp, sample0=sample0)
-        self._cutouts(cands, sample0)              # the block of the last push() is still the searcher's current one
+        self._cutouts(cands, sample0)
         self._refine(cands, sample0)
+        return cands
+
+    def _finish(self):
+        if self.pending is None:
+            return []
+        early = getattr(self, "early", None)
+        cands = early if early is not None else self._pending_cands()
+        _, sample0, tout = self.pending
+        self.pending = None
         self.last_first = self.done
         self._send(cands, self.done, tout - (self.done - sample0))
         self.done = sample0 + tout
@@ -631,6 +821,7 @@ def arg_parser():
     ap.add_argument("-cand_sep_dm", type=int, default=200, help="with -giants: trial DMs between linked giants")
     ap.add_argument("-cand_sep_filter", type=int, default=3, help="with -giants: log2 boxcar widths between linked giants")
     ap.add_argument("-max_giants", type=int, default=1 << 18, help="with -giants: a gulp with more giants is given up")
+    ap.add_argument("-stream_chunk", type=int, default=0, help="> 0: read the file in pieces of this many samples and gather each gulp on the GPU; 8-, 4- and 2-bit files")
     return ap
 
 
@@ -654,6 +845,8 @@ def parse_args(argv=None):
         ap.error("-cand_sep_dm and -cand_sep_filter must be >= 0")
     if not 1 <= a.max_giants <= 1 << 22:
         ap.error("-max_giants must be in 1..4194304")
+    if a.stream_chunk < 0:
+        ap.error("-stream_chunk must be >= 0")
     return a
 
 
@@ -714,13 +907,20 @@ def main(argv=None):
     gulp that has candidates also gets a .cand file of the same lines, with -cutouts a .cutouts.npz beside it, with
     -refine a .refined file (the refined candidates' lines, each followed by refined DM, S/N, width and peak sample).
     -giants takes the candidates from the GPU's giants and clusters (heimdall's -cand_sep_time / -cand_sep_dm /
-    -cand_sep_filter; this project's own definition) instead of the host's grouping of the point list."""
+    -cand_sep_filter; this project's own definition) instead of the host's grouping of the point list.
+    -stream_chunk M reads the file in pieces of M samples and feeds them to GulpSearch(gulp=-nsamps_gulp): the same
+    lines, gathered on the GPU as a host behind pb_process would gather them; on this path 4- and 2-bit files are
+    accepted and fed packed."""
     import os
     sig = importlib.import_module(_pkg + ".sigproc")
     a = parse_args(argv)
     with open(a.fil, "rb") as f:
         hdr, off = sig.read_header(f.read(4096))
-    if hdr["nbits"] != 8 or hdr.get("nifs", 1) != 1:
+    nbits = hdr["nbits"]
+    if a.stream_chunk:
+        if nbits not in (8, 4, 2) or hdr.get("nifs", 1) != 1 or (hdr["nchans"] * nbits) % 8:
+            raise SystemExit("search -stream_chunk: 8-, 4- or 2-bit single-IF filterbanks whose time samples fill whole bytes only")
+    elif nbits != 8 or hdr.get("nifs", 1) != 1:
         raise SystemExit("search: 8-bit single-IF filterbanks only")
     nchan, tsamp = hdr["nchans"], hdr["tsamp"]
     zap = tuple(tuple(z) for z in a.zap_chans) if a.zap_chans else ()
@@ -748,7 +948,7 @@ def main(argv=None):
     gi = dict(sep_time=a.cand_sep_time, sep_dm=a.cand_sep_dm, sep_filter=a.cand_sep_filter,
               max_giants=a.max_giants) if a.giants else None
     g = GulpSearch(s, threshold=a.detect_thresh, coincidencer=a.coincidencer, utc_start=utc, beam=a.beam, cutouts=cut,
-                   refine=ref, giants=gi)
+                   refine=ref, giants=gi, gulp=a.nsamps_gulp if a.stream_chunk else None)
     if a.output_dir:
         os.makedirs(a.output_dir, exist_ok=True)
     ntot, stems = 0, set()
@@ -771,7 +971,14 @@ def main(argv=None):
 
     with open(a.fil, "rb") as f:
         f.seek(off)
-        while True:
+        rowb = nchan * nbits // 8
+        while a.stream_chunk:
+            blk = np.frombuffer(f.read(a.stream_chunk * rowb), np.uint8)
+            if blk.size < rowb:
+                ntot += emit(g.flush())
+                break
+            ntot += emit(g.feed(blk[:blk.size // rowb * rowb], nbit=nbits))
+        while not a.stream_chunk:
             blk = np.frombuffer(f.read(a.nsamps_gulp * nchan), np.uint8)
             if blk.size < nchan:
                 break
