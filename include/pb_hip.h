@@ -577,6 +577,32 @@ int pb_search_giant_timers(const pb_search *s, float *ms3, int *nsweeps);
  * tests/test_gpu_search_stream.py: the block equals the unpacked concatenation of the pieces however they are cut,
  * packed and placed, and a stream fed in pieces gives the candidates of the same stream searched in whole host gulps. */
 int pb_search_set_gulp(pb_search *s, int keep_max);
+/* The same append from an fp32 plane, quantised to 8 bits on the way: the search at 8-bit depth behind a filterbank that
+ * writes 2 or 4 bits.  `plane` is nsamp samples in SIGPROC order [time][nchan] of binary32 -- pb_output_dev's `ave` at
+ * npol = 1 (needs keep_ave; contiguous over a batch's segments), or a coadder's d_sum.  For t in [0, nsamp), c in
+ * [0, nchan), every line one binary32 or binary64 operation, none contracted with another:
+ *     v   = plane[t * nchan + c] * scale                      (binary32)
+ *     tmp = (float)((double)v / 0.02957 + 127.5)              (binary64 quotient, binary64 sum, rounded to binary32)
+ *     q   = tmp > 0 ? (tmp >= 255 ? 255 : (uint8_t)tmp) : 0   (the cast truncates)
+ *     xt[c][fill + t] = q
+ * then fill += nsamp; *fill (may be NULL) = the new fill.  For every v that is not a NaN this is sel_and_dig_8b
+ * (src/pb_kernels.cu:711-735), the arithmetic of pb_coadd_digitise at 8 bits: with scale = 1 the block is the one that
+ * an nbit = 8 handle's codes would have given, with scale = (float)(1 / sqrt(N)) the one that pb_coadd_finish's codes
+ * would.  A NaN (a segment of dropped frames, tools/nan_codes_check.py) gives 0: the comparison is written `tmp > 0`.
+ * scale must be finite and > 0 (1 is exact).
+ * plane_on_device = 1: read where it lies under the contract of pb_search_run (the caller synchronises the producer;
+ * valid until return; nothing read outside [plane, plane + nsamp * nchan)); the address must be a multiple of 4, and one
+ * that is a multiple of 16 with nchan a multiple of 4 is read with 16-byte loads -- the result is the same.
+ * plane_on_device = 0: host floats, staged through the buffer that pb_search_run stages its host blocks through
+ * (max_samples * nchan bytes) in slices of max_samples / 4 samples; nothing more is allocated.  The call returns when the
+ * plane has been consumed.  pb_search_gulp_timers reports it like a pb_search_push (the slices' times added up).
+ * Pushes of planes and of codes of any depth may alternate within one gulp; a handle on which this is never called
+ * allocates and launches what it did before.  Refused (PB_EINVAL, fill and block unchanged): what pb_search_push refuses
+ * (the stage off, no handle, nsamp < 0, fill + nsamp > max_samples, a block cleaned in place); a scale that is not
+ * finite or not > 0; a device plane at an address that is not a multiple of 4.
+ * tests/test_gpu_search_plane.py: the block equals the NumPy restatement (tests/search_plane_ref.py, itself pinned to
+ * the oracle's sel_and_dig_8b) for every alignment, source and scale. */
+int pb_search_push_f32(pb_search *s, const float *plane, int plane_on_device, int nsamp, float scale, int *fill);
 int pb_search_push(pb_search *s, const void *codes, int codes_on_device, int nsamp, int nbit, int *fill);
 int pb_search_gulp_peaks(pb_search *s, float threshold, int32_t *peaks, int max_out, int *npeaks, int *tout);
 int pb_search_gulp_run(pb_search *s, float *snr, uint8_t *width_log2, uint32_t *series, float *stats, int *tout);

@@ -65,6 +65,35 @@ __device__ __forceinline__ void gather_shift(const uint32_t (&w)[NDW + 1], unsig
     for (int i = 0; i < NDW; ++i) a[i] = gather_align(w[i], w[i + 1], sh);
 }
 
+// ---- the append of the streaming stage (search_stream.hip: codes; search_plane.hip: an fp32 plane) ----
+// Both tile the DESTINATION: a tile is SA_T block samples from a multiple of SA_T on, staged in LDS as [sample][channel]
+// and stored along time, sixteen samples of one channel at a time.
+#define SA_T 64                 // destination samples of a tile
+#define SA_B 64                 // fast path of the codes: packed source bytes of a tile's row
+#define SA_PITCH 84             // fast path of the codes: LDS pitch of a tile row in bytes; 16 rows = 336 dwords = 16 banks on:
+                                // the four 16-sample groups that a wave reads together fall into different banks
+#define SA_BPITCH 68            // 64 unpacked channels: the same (16 rows = 272 dwords = 16 banks on)
+
+// w = 16 samples of one channel from sample td (a multiple of 16) on; [lo, hi) = the samples that this push owns
+__device__ __forceinline__ void stream_store16(uint8_t *__restrict__ row, int td, int lo, int hi, const uint32_t (&w)[4])
+{
+    if (td >= lo && td + 16 <= hi) {
+        *(uint4 *)(row + td) = make_uint4(w[0], w[1], w[2], w[3]);
+        return;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int tq = td + 4 * q;
+        if (tq >= lo && tq + 4 <= hi) {
+            *(uint32_t *)(row + tq) = w[q];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (tq + k >= lo && tq + k < hi) row[tq + k] = (uint8_t)(w[q] >> (8 * k));
+        }
+    }
+}
+
 // ---- a workgroup of 256 threads ----
 
 // op over the workgroup's values, the same in every thread; sh: 4 words of LDS.  The order is fixed (k_series_stats'

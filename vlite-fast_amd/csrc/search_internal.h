@@ -1,7 +1,7 @@
 // What the search's translation units share on the host side: the handle, the dispersion delay, the error and timer
 // helpers, and each stage's free function.  search_run.hip holds the core (create .. fetch_clean) and the RFI cleaning;
 // search_cutout.hip, search_refine.hip, search_giants.hip and search_stream.hip one optional stage each, kernels and host side together (a
-// kernel lives in the file that launches it).  Device-only helpers: search_dev.h.
+// kernel lives in the file that launches it); search_plane.hip the streaming stage's entry for fp32 planes.  Device-only helpers: search_dev.h.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -20,32 +20,7 @@
 //
 // The tail needs no kernel: it is two 2-D device copies through the side buffer d_tail, [nchan][keep_max].
 #include "search_internal.h"
-
-#define SA_T 64                 // destination samples of a tile
-#define SA_B 64                 // fast path: packed source bytes of a tile's row
-#define SA_PITCH 84             // fast path: LDS pitch of a tile row in bytes; 16 rows = 336 dwords = 16 banks on: the four
-                                // 16-sample groups that a wave reads together fall into different banks
-#define SA_BPITCH 68            // byte path: the same for 64 unpacked channels (16 rows = 272 dwords = 16 banks on)
-
-// w = 16 samples of one channel from sample td (a multiple of 16) on; [lo, hi) = the samples that this push owns
-__device__ __forceinline__ void stream_store16(uint8_t *__restrict__ row, int td, int lo, int hi, const uint32_t (&w)[4])
-{
-    if (td >= lo && td + 16 <= hi) {
-        *(uint4 *)(row + td) = make_uint4(w[0], w[1], w[2], w[3]);
-        return;
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int tq = td + 4 * q;
-        if (tq >= lo && tq + 4 <= hi) {
-            *(uint32_t *)(row + tq) = w[q];
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (tq + k >= lo && tq + k < hi) row[tq + k] = (uint8_t)(w[q] >> (8 * k));
-        }
-    }
-}
+#include "search_dev.h"         // the tile constants SA_* and stream_store16, shared with search_plane.hip
 
 // codes: [nsamp][rowb] packed bytes, 16-byte aligned, rowb = nchan * NBIT / 8 a multiple of 16 -> xt[c][fill + t]
 template <int NBIT>

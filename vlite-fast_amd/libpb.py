@@ -58,7 +58,7 @@ EXPORTS = ["pb_config_default", "pb_create", "pb_destroy", "pb_last_error", "pb_
            "pb_search_timers", "pb_search_set_rfi", "pb_search_rfi_info", "pb_search_fetch_clean", "pb_search_set_cutouts",
            "pb_search_cutouts", "pb_search_cutout_timers", "pb_search_set_refine", "pb_search_refine",
            "pb_search_refine_timers", "pb_search_set_giants", "pb_search_giants", "pb_search_giant_list",
-           "pb_search_set_planes", "pb_search_giant_timers", "pb_search_set_gulp", "pb_search_push", "pb_search_gulp_peaks",
+           "pb_search_set_planes", "pb_search_giant_timers", "pb_search_set_gulp", "pb_search_push", "pb_search_push_f32", "pb_search_gulp_peaks",
            "pb_search_gulp_run", "pb_search_gulp_advance", "pb_search_gulp_fetch", "pb_search_gulp_timers"]
 
 _lib = None
@@ -162,6 +162,7 @@ def load():
     L.pb_search_giant_timers.argtypes = [vp, fp, ip]
     L.pb_search_set_gulp.argtypes = [vp, C.c_int]
     L.pb_search_push.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, ip]
+    L.pb_search_push_f32.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, ip]
     L.pb_search_gulp_peaks.argtypes = [vp, C.c_float, i32p, C.c_int, ip, ip]
     L.pb_search_gulp_run.argtypes = [vp, fp, u8p, u32p, fp, ip]
     L.pb_search_gulp_advance.argtypes = [vp, C.c_int]

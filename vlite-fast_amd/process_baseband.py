@@ -109,7 +109,19 @@ def build_parser():
     p.add_argument("--rows-per-seg", type=int, default=1024, help="test hook: shorter segments")
     p.add_argument("--coherence", action="store_true",
                    help="with -P 2: write AA, BB, CR, CI (nifs 4, NPOL 4) instead of AA, BB")
+    p.add_argument("--search", default=None, metavar="FLAGS",
+                   help="search the stream that ring -K gets in this process, where it lies on the GPU: the flags of "
+                        "`python -m vlite-fast_amd.search` in one string, less -f and -stream_chunk")
+    p.add_argument("--search-input", choices=["plane", "codes"], default="plane",
+                   help="with --search: the fp32 plane before quantisation at 8-bit depth (default), or the -b codes")
     return p
+
+
+def search_flags(args):
+    """the parsed flags of --search (search.parse_flags: the search's own parser), None without it"""
+    if getattr(args, "search", None) is None:
+        return None
+    return importlib.import_module(_pkg + ".search").parse_flags(args.search)
 
 
 def validate(args):
@@ -121,6 +133,10 @@ def validate(args):
         raise SystemExit("Unsupported npol!")
     if getattr(args, "coherence", False) and args.npol != 2:
         raise SystemExit("--coherence needs -P 2")
+    if getattr(args, "search", None) is not None:
+        if args.npol != 1 or getattr(args, "coherence", False):
+            raise SystemExit("--search takes one [time][4096] stream: not with -P 2 or --coherence")
+        search_flags(args)               # (a bad flag ends the run here, with the search's own message)
     if args.rows_per_seg == 1024 and args.gpu_id not in (0, 1, 2, 3, 4, 5, 6, 7):
         raise SystemExit("Unsupported GPU id!")
 
@@ -301,12 +317,17 @@ def run(args, in_ring=None, out_ring=None, co_ring=None, handle=None, control_so
         out_ring = dada.FileSink(args.out_sink) if args.out_sink else dada.open_ring(args.key_out, "w")
     if co_ring is None and (args.co_sink or args.key_co):
         co_ring = dada.FileSink(args.co_sink) if args.co_sink else dada.open_ring(args.key_co, "w")
+    sflags = search_flags(args)          # None without --search: no Searcher, keep_ave off, every byte as before
+    from_plane = sflags is not None and args.search_input == "plane"
+    searcher = gsearch = emit = None     # one Searcher per process, one GulpSearch per observation
     own_handle = handle is None
     if handle is None:
         handle = lp.PbHandle(device=args.gpu_id, nant=1, nbit=args.nbit, npol=args.npol, rfi_mode=args.rfi_mode,
                              taps=args.taps, fft_backend=lp.FFT_LDS if args.fft_backend == "lds" else lp.FFT_HIPFFT,
                              rows_per_seg=R, max_seg=SEG_PER_SEC, inject_frb=args.inject_frb, nsets=2,
-                             coherence=getattr(args, "coherence", False))
+                             coherence=getattr(args, "coherence", False), keep_ave=from_plane)
+    elif from_plane and not handle.cfg.keep_ave:
+        raise SystemExit("--search-input plane needs a handle made with keep_ave")
     trim = handle.trim
     nsets = handle.nsets
     ctl = control_sock if control_sock is not None else (None if args.no_control else open_control_socket())
@@ -380,6 +401,13 @@ def run(args, in_ring=None, out_ring=None, co_ring=None, handle=None, control_so
         if fb_kur_fp:
             fb_kur_fp.write(sp_hdr)
 
+        if sflags is not None:
+            # the band and the start time that the SIGPROC header carries, so that the candidates and their files'
+            # names are those of `search -f` on the file
+            smod = importlib.import_module(_pkg + ".search")
+            searcher, gsearch, emit = smod.open_search(sflags, sigproc.read_header(sp_hdr)[0], sflags.nsamps_gulp,
+                                                       device=args.gpu_id, searcher=searcher)
+
         current_sec = vh["second"]
         log("INFO", "Starting sec=%d, thread=%d" % (current_sec, vh["thread"]))
         st = dict(integrated_sec=0, fb_bytes=0, t_rt=time.time())
@@ -396,6 +424,14 @@ def run(args, in_ring=None, out_ring=None, co_ring=None, handle=None, control_so
             out = handle.fetch(0, 0, SEG_PER_SEC, raw=args.rfi_mode != 1, kur=args.rfi_mode != 0)
             main_codes = out["raw"] if args.rfi_mode != 1 else out["kur"]
             heim_codes = out["kur"] if args.rfi_mode != 0 else out["raw"]
+            if gsearch is not None:
+                # the stream that ring -K gets, where it lies: pb_fetch has waited for this set's detect and copy-out
+                # (ev_det), so its code bytes and fp32 plane are complete, and they stay until this set's next pb_process
+                d_codes, d_ave = handle.output_dev(0, 1 if args.rfi_mode != 0 else 0)
+                if from_plane:
+                    emit(gsearch.feed_plane(device_ptr=d_ave, nsamp=SEG_PER_SEC * R // 8))
+                else:
+                    emit(gsearch.feed(nbit=args.nbit, device_ptr=d_codes, nsamp=SEG_PER_SEC * R // 8))
             for iseg in range(SEG_PER_SEC):
                 sl = slice(iseg * trim, (iseg + 1) * trim)
                 if co_ring is not None:
@@ -459,6 +495,10 @@ def run(args, in_ring=None, out_ring=None, co_ring=None, handle=None, control_so
         while st["integrated_sec"] < queued:
             collect(st["integrated_sec"])
         integrated_sec, fb_bytes = st["integrated_sec"], st["fb_bytes"]
+        if gsearch is not None:
+            emit(gsearch.flush())
+            emit(gsearch.finish())
+            gsearch = None
 
         if out_ring is not None:
             out_ring.end_of_data()
@@ -488,6 +528,8 @@ def run(args, in_ring=None, out_ring=None, co_ring=None, handle=None, control_so
         written_files.append((fb, fb_kur if args.rfi_mode == 2 else None))
         if args.profile_pass or args.single_pass:
             break
+    if searcher is not None:
+        searcher.close()
     if own_handle:
         handle.close()
     run.last_files = written_files

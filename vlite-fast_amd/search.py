@@ -373,6 +373,28 @@ class Searcher(object):
         self._check(rc, "pb_search_push")
         return fill.value
 
+    def push_plane(self, plane=None, device_ptr=None, nsamp=None, scale=1.0):
+        """append a piece of an fp32 plane [nsamp][nchan], quantised to 8 bits with the reference's rule on the device
+        (include/pb_hip.h, pb_search_push_f32: q = trunc(float(double(x * scale) / 0.02957 + 127.5)) clamped to 0..255,
+        NaN -> 0): a host float32 array, or device_ptr + nsamp for floats that are already on the GPU (PbHandle.output_dev's
+        `ave` with keep_ave, a coadder's sum with scale = float32(1 / sqrt(N)); the contract of run(), the address a
+        multiple of 4).  Returns the block's new length in samples."""
+        if device_ptr is None:
+            plane = np.ascontiguousarray(plane, np.float32).ravel()
+            if nsamp is None:
+                nsamp = plane.size // self.nchan
+            elif plane.size < int(nsamp) * self.nchan:
+                raise ValueError("plane holds fewer than nsamp samples")
+            ptr, on_dev = plane.ctypes.data_as(C.c_void_p), 0
+        else:
+            if nsamp is None:
+                raise ValueError("device_ptr needs nsamp")
+            ptr, on_dev = C.c_void_p(device_ptr), 1
+        fill = C.c_int()
+        rc = self._L.pb_search_push_f32(self._s, ptr, on_dev, int(nsamp), C.c_float(float(scale)), C.byref(fill))
+        self._check(rc, "pb_search_push_f32")
+        return fill.value
+
     def gulp_peaks(self, threshold, max_out=1 << 18):
         """peaks() on the accumulated block: the same dict"""
         buf = np.empty((max_out, 4), np.int32)
@@ -585,8 +607,9 @@ class GulpSearch(object):
     gathered on the device (Searcher.set_gulp / push): every N new samples the accumulated block is searched as push()
     searches a block of N new samples, and its last max_delay + widest - 1 raw samples are handed on without leaving the
     device.  feed(p1) .. feed(pk) + finish() return, in order, the candidates of push(b1) .. push(bm) + finish() over
-    the same stream cut into blocks of N, the remainder last (tests/test_gpu_search_stream.py).  gulp=None (default):
-    push() only."""
+    the same stream cut into blocks of N, the remainder last (tests/test_gpu_search_stream.py).  feed_plane() takes a
+    piece as an fp32 plane instead, quantised to 8 bits on the device (Searcher.push_plane), and may alternate with
+    feed().  gulp=None (default): push() only."""
 
     def __init__(self, searcher, threshold=6.0, nbit=8, coincidencer=None, utc_start="1970-01-01-00:00:00", beam=1,
                  cutouts=None, refine=None, giants=None, gulp=None):
@@ -737,12 +760,34 @@ class GulpSearch(object):
                 raise ValueError("codes holds fewer than nsamp samples")
         elif nsamp is None:
             raise ValueError("device_ptr needs nsamp")
+        if device_ptr is None:
+            return self._feed(nsamp, lambda off, n: self.s.push(codes[off * rowb:(off + n) * rowb], nbit=nbit, nsamp=n))
+        return self._feed(nsamp, lambda off, n: self.s.push(nbit=nbit, device_ptr=device_ptr + off * rowb, nsamp=n))
+
+    def feed_plane(self, plane=None, device_ptr=None, nsamp=None, scale=1.0):
+        """feed() for a piece of an fp32 plane [nsamp][nchan] (Searcher.push_plane: quantised to 8 bits on the device) --
+        a host float32 array, or device_ptr + nsamp.  The same cuts, fires and returns; feed() and feed_plane() may
+        alternate on one stream."""
+        if self.gulp is None:
+            raise ValueError("feed_plane() needs GulpSearch(gulp=N)")
+        nchan = self.s.nchan
+        if device_ptr is None:
+            plane = np.ascontiguousarray(plane, np.float32).ravel()
+            if nsamp is None:
+                nsamp = plane.size // nchan
+            if plane.size < nsamp * nchan:
+                raise ValueError("plane holds fewer than nsamp samples")
+            return self._feed(nsamp, lambda off, n: self.s.push_plane(plane[off * nchan:(off + n) * nchan], nsamp=n, scale=scale))
+        if nsamp is None:
+            raise ValueError("device_ptr needs nsamp")
+        return self._feed(nsamp, lambda off, n: self.s.push_plane(device_ptr=device_ptr + 4 * off * nchan, nsamp=n, scale=scale))
+
+    def _feed(self, nsamp, push):
+        """a piece of nsamp samples cut where the gulps end: push(first sample, length) appends a part and returns the
+        block's new length; a fire follows each part that completes a gulp"""
         out = []
         for off, n, fire in gulp_cuts(self.since, nsamp, self.gulp):
-            if device_ptr is None:
-                self.fill = self.s.push(codes[off * rowb:(off + n) * rowb], nbit=nbit, nsamp=n)
-            else:
-                self.fill = self.s.push(nbit=nbit, device_ptr=device_ptr + off * rowb, nsamp=n)
+            self.fill = push(off, n)
             self.since += n
             if fire:
                 out += self._fire()
@@ -789,11 +834,13 @@ def candidate_line(c):
     return importlib.import_module((__package__ or "vlite-fast_amd") + ".candidates").candidate_line(c)
 
 
-def arg_parser():
-    """the command line of main(): heimdall's flag names"""
+def arg_parser(with_file=True):
+    """the command line of main(): heimdall's flag names.  with_file=False: the flags that a host which feeds the search
+    itself accepts (process_baseband --search) -- the same ones less -f and -stream_chunk."""
     import argparse
-    ap = argparse.ArgumentParser(prog="search", prefix_chars="-")
-    ap.add_argument("-f", dest="fil", required=True)
+    ap = argparse.ArgumentParser(prog="search" if with_file else "--search", prefix_chars="-")
+    if with_file:
+        ap.add_argument("-f", dest="fil", required=True)
     ap.add_argument("-dm", nargs=2, type=float, default=list(HEIMDALL_DM))
     ap.add_argument("-dm_tol", type=float, default=1.25)
     ap.add_argument("-dm_step", type=float, default=0.0, help="> 0: linear grid instead of the tolerance-spaced list")
@@ -821,13 +868,21 @@ def arg_parser():
     ap.add_argument("-cand_sep_dm", type=int, default=200, help="with -giants: trial DMs between linked giants")
     ap.add_argument("-cand_sep_filter", type=int, default=3, help="with -giants: log2 boxcar widths between linked giants")
     ap.add_argument("-max_giants", type=int, default=1 << 18, help="with -giants: a gulp with more giants is given up")
-    ap.add_argument("-stream_chunk", type=int, default=0, help="> 0: read the file in pieces of this many samples and gather each gulp on the GPU; 8-, 4- and 2-bit files")
+    if with_file:
+        ap.add_argument("-stream_chunk", type=int, default=0, help="> 0: read the file in pieces of this many samples and gather each gulp on the GPU; 8-, 4- and 2-bit files")
     return ap
 
 
-def parse_args(argv=None):
+def parse_flags(flags):
+    """process_baseband's --search "<flags>": the string split as a shell would and parsed by the search's own parser
+    (arg_parser(with_file=False) and parse_args' checks); an unknown flag, -f or -stream_chunk ends in SystemExit"""
+    import shlex
+    return parse_args(shlex.split(flags), with_file=False)
+
+
+def parse_args(argv=None, with_file=True):
     """arg_parser() plus the checks between flags"""
-    ap = arg_parser()
+    ap = arg_parser(with_file)
     a = ap.parse_args(argv)
     if a.cutouts and not a.output_dir:
         ap.error("-cutouts needs -output_dir")
@@ -845,7 +900,7 @@ def parse_args(argv=None):
         ap.error("-cand_sep_dm and -cand_sep_filter must be >= 0")
     if not 1 <= a.max_giants <= 1 << 22:
         ap.error("-max_giants must be in 1..4194304")
-    if a.stream_chunk < 0:
+    if with_file and a.stream_chunk < 0:
         ap.error("-stream_chunk must be >= 0")
     return a
 
@@ -898,41 +953,28 @@ def gulp_stem(utc_start, first_sample, tsamp, beam):
     return "%s_%02d" % (_time.strftime("%Y-%m-%d-%H:%M:%S", _time.gmtime(t0 + int(first_sample * tsamp))), beam)
 
 
-def main(argv=None):
-    """heimdall's place in the chain for a SIGPROC file: `python -m vlite-fast_amd.search -f obs_kur.fil
-    -dm 2 1000 -boxcar_max 64 -nsamps_gulp 30720 -zap_chans 0 190 -zap_chans 3900 4096 -rfi_clean
-    -giants -output_dir /mnt/ssd/cands -cutouts -coincidencer vlite-nrl:27555` (the flags of
-    scripts/start_heimdall_single_antenna:21; that launch leaves heimdall's RFI cleaning on, which here is -rfi_clean).
-    Prints heimdall-format candidate lines per gulp and, with -coincidencer, sends them there; with -output_dir each
-    gulp that has candidates also gets a .cand file of the same lines, with -cutouts a .cutouts.npz beside it, with
-    -refine a .refined file (the refined candidates' lines, each followed by refined DM, S/N, width and peak sample).
-    -giants takes the candidates from the GPU's giants and clusters (heimdall's -cand_sep_time / -cand_sep_dm /
-    -cand_sep_filter; this project's own definition) instead of the host's grouping of the point list.
-    -stream_chunk M reads the file in pieces of M samples and feeds them to GulpSearch(gulp=-nsamps_gulp): the same
-    lines, gathered on the GPU as a host behind pb_process would gather them; on this path 4- and 2-bit files are
-    accepted and fed packed."""
+def open_search(a, hdr, gulp, device=None, searcher=None):
+    """What main() and a host that feeds the search itself (process_baseband --search) share: the Searcher and the
+    GulpSearch that the flags `a` (parse_args) ask for, for a stream whose SIGPROC header is `hdr` (nchans, fch1, foff,
+    tsamp, tstart), and the writer of a batch of candidates.  gulp: GulpSearch's (None: whole host gulps through push()).
+    device: instead of -gpu_id.  searcher: one made by an earlier call with the same flags and band, used again (a host's
+    next observation).  Returns (searcher, gulp_search, emit); emit(cands) prints the candidates' lines, writes the
+    -output_dir files of the batch that gulp_search has just returned, and returns how many there were."""
     import os
-    sig = importlib.import_module(_pkg + ".sigproc")
-    a = parse_args(argv)
-    with open(a.fil, "rb") as f:
-        hdr, off = sig.read_header(f.read(4096))
-    nbits = hdr["nbits"]
-    if a.stream_chunk:
-        if nbits not in (8, 4, 2) or hdr.get("nifs", 1) != 1 or (hdr["nchans"] * nbits) % 8:
-            raise SystemExit("search -stream_chunk: 8-, 4- or 2-bit single-IF filterbanks whose time samples fill whole bytes only")
-    elif nbits != 8 or hdr.get("nifs", 1) != 1:
-        raise SystemExit("search: 8-bit single-IF filterbanks only")
+    import time as _time
     nchan, tsamp = hdr["nchans"], hdr["tsamp"]
-    zap = tuple(tuple(z) for z in a.zap_chans) if a.zap_chans else ()
-    dml = None if a.dm_step > 0 else dedisp_dm_list(a.dm[0], a.dm[1], tsamp, hdr["fch1"], hdr["foff"], nchan, a.dm_tol)
-    kw = dict(device=a.gpu_id, nchan=nchan, fch1=hdr["fch1"], foff=hdr["foff"], tsamp=tsamp, boxcar_max=a.boxcar_max, zap=zap)
     maxs = a.nsamps_gulp + int(4.148808e3 * a.dm[1] * abs((hdr["fch1"] + (nchan - 1) * hdr["foff"]) ** -2
                                                          - hdr["fch1"] ** -2) / tsamp) + 64
-    s = Searcher(max_samples=maxs, dm_list=dml, dm_min=a.dm[0], dm_max=a.dm[1], dm_step=a.dm_step or 2.0, **kw)
-    s.set_baseline(int(a.baseline_length / tsamp))
-    if a.rfi_clean:
-        s.set_rfi(narrow=not a.rfi_no_narrow, broad=not a.rfi_no_broad, tol=a.rfi_tol)
-    import time as _time
+    s = searcher
+    if s is None:
+        zap = tuple(tuple(z) for z in a.zap_chans) if a.zap_chans else ()
+        dml = None if a.dm_step > 0 else dedisp_dm_list(a.dm[0], a.dm[1], tsamp, hdr["fch1"], hdr["foff"], nchan, a.dm_tol)
+        kw = dict(device=a.gpu_id if device is None else device, nchan=nchan, fch1=hdr["fch1"], foff=hdr["foff"], tsamp=tsamp,
+                  boxcar_max=a.boxcar_max, zap=zap)
+        s = Searcher(max_samples=maxs, dm_list=dml, dm_min=a.dm[0], dm_max=a.dm[1], dm_step=a.dm_step or 2.0, **kw)
+        s.set_baseline(int(a.baseline_length / tsamp))
+        if a.rfi_clean:
+            s.set_rfi(narrow=not a.rfi_no_narrow, broad=not a.rfi_no_broad, tol=a.rfi_tol)
     utc = _time.strftime("%Y-%m-%d-%H:%M:%S", _time.gmtime(round((hdr.get("tstart", 40587.0) - 40587.0) * 86400.0)))
     cut = None
     if a.cutouts:
@@ -948,10 +990,10 @@ def main(argv=None):
     gi = dict(sep_time=a.cand_sep_time, sep_dm=a.cand_sep_dm, sep_filter=a.cand_sep_filter,
               max_giants=a.max_giants) if a.giants else None
     g = GulpSearch(s, threshold=a.detect_thresh, coincidencer=a.coincidencer, utc_start=utc, beam=a.beam, cutouts=cut,
-                   refine=ref, giants=gi, gulp=a.nsamps_gulp if a.stream_chunk else None)
+                   refine=ref, giants=gi, gulp=gulp)
     if a.output_dir:
         os.makedirs(a.output_dir, exist_ok=True)
-    ntot, stems = 0, set()
+    stems = set()
 
     def emit(cands):
         for c in cands:
@@ -968,6 +1010,35 @@ def main(argv=None):
             if a.refine:
                 write_refined(os.path.join(a.output_dir, stem + ".refined"), cands)
         return len(cands)
+
+    return s, g, emit
+
+
+def main(argv=None):
+    """heimdall's place in the chain for a SIGPROC file: `python -m vlite-fast_amd.search -f obs_kur.fil
+    -dm 2 1000 -boxcar_max 64 -nsamps_gulp 30720 -zap_chans 0 190 -zap_chans 3900 4096 -rfi_clean
+    -giants -output_dir /mnt/ssd/cands -cutouts -coincidencer vlite-nrl:27555` (the flags of
+    scripts/start_heimdall_single_antenna:21; that launch leaves heimdall's RFI cleaning on, which here is -rfi_clean).
+    Prints heimdall-format candidate lines per gulp and, with -coincidencer, sends them there; with -output_dir each
+    gulp that has candidates also gets a .cand file of the same lines, with -cutouts a .cutouts.npz beside it, with
+    -refine a .refined file (the refined candidates' lines, each followed by refined DM, S/N, width and peak sample).
+    -giants takes the candidates from the GPU's giants and clusters (heimdall's -cand_sep_time / -cand_sep_dm /
+    -cand_sep_filter; this project's own definition) instead of the host's grouping of the point list.
+    -stream_chunk M reads the file in pieces of M samples and feeds them to GulpSearch(gulp=-nsamps_gulp): the same
+    lines, gathered on the GPU as a host behind pb_process would gather them; on this path 4- and 2-bit files are
+    accepted and fed packed."""
+    sig = importlib.import_module(_pkg + ".sigproc")
+    a = parse_args(argv)
+    with open(a.fil, "rb") as f:
+        hdr, off = sig.read_header(f.read(4096))
+    nbits = hdr["nbits"]
+    if a.stream_chunk:
+        if nbits not in (8, 4, 2) or hdr.get("nifs", 1) != 1 or (hdr["nchans"] * nbits) % 8:
+            raise SystemExit("search -stream_chunk: 8-, 4- or 2-bit single-IF filterbanks whose time samples fill whole bytes only")
+    elif nbits != 8 or hdr.get("nifs", 1) != 1:
+        raise SystemExit("search: 8-bit single-IF filterbanks only")
+    s, g, emit = open_search(a, hdr, a.nsamps_gulp if a.stream_chunk else None)
+    nchan, ntot = hdr["nchans"], 0
 
     with open(a.fil, "rb") as f:
         f.seek(off)
