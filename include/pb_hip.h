@@ -468,6 +468,77 @@ int pb_search_refine(pb_search *s, const int32_t *req_i2, const float *req_f2, i
 /* device time of the last pb_search_refine in ms: the three kernels; the kernels and the copy to the host */
 int pb_search_refine_timers(const pb_search *s, float *ms2);
 
+/* Polarisation of a candidate: the search on the four-product filterbank that pb_create's `coherence` writes (AA, BB, CR,
+ * CI; SIGPROC nifs 4), and for the candidates of a block -- from what is still on the device -- the four frequency-time
+ * images, the on- and off-pulse spectra and an RM synthesis over a grid of trial rotation measures.  The definition is
+ * THIS project's own.  Off until pb_search_set_pol; a pb_search on which it was never called allocates nothing more,
+ * launches nothing more and returns the bytes it returns without it.
+ * Notation: nsamp, tout, delay[dm][c], the unzapped channels (nact of them) as under pb_search_set_cutouts;
+ * f_c = fch1 + c foff in MHz (double, from the binary32 band of pb_search_create); lambda2_c = (299.792458 / f_c)^2 in m^2,
+ * in double as written (one quotient, one product).
+ * Input.  While the stage is on, every block given to pb_search_run / pb_search_peaks is [nsamp][4][nchan] 8-bit codes, the
+ * four in the order AA, BB, CR, CI -- the row order of a nifs 4 SIGPROC file -- nsamp * 4 * nchan bytes, for host and device
+ * pointers alike (the contract of codes_on_device = 1 holds; a device block whose address and nchan are multiples of 4 is
+ * read with 4-byte loads, any other byte by byte, the result is the same).  Refused, PB_EINVAL with nothing launched or
+ * written: nbit != 8 while the stage is on; pb_search_push, pb_search_push_f32 and the pb_search_gulp_* calls while it is on
+ * (streaming cannot be on with it: pb_search_set_gulp is refused while this stage is on, and this stage while streaming
+ * is).  Searching 4-IF data in the streaming path is left for later.
+ * Planes.  k_transpose_pol turns the block into five channel-major u8 planes of the search's pitch: xa, xb, xcr, xci,
+ * each [c][t], and the search plane xt[c][t] = (aa + bb + 1) >> 1, the rounded mean in integer arithmetic: total intensity
+ * at 8-bit depth (255 and 255 give 255).  From xt on the search is byte for byte what it is on a 1-IF block of those
+ * codes: RFI cleaning, dedispersion, statistics, boxcars, peaks, giants, cutouts and refinement all read xt.  RFI cleaning
+ * changes xt ONLY: the four product planes are what the file held, flagged samples included.
+ * Images.  Geometry (nsub, nt) and request (dmi, t_pk, tscr) of pb_search_set_cutouts.  pft[k][s][j], k = 0..3, is exactly
+ * ft[s][j] of that definition with the plane of product k in place of xt; pft_hits[s][j] is ft_hits, the same for all four.
+ * Spectra.  A request is (dmi, t_pk, w), w in 1..64.  The on window is T_on = [t_pk, t_pk + w); the off windows are
+ * [t_pk - g - L, t_pk - g) and [t_pk + w + g, t_pk + w + g + L), guard g in 0..1024 and off length L in 1..1024 set with the
+ * stage.  For every unzapped channel c and product k: on[k][c] = sum over t in T_on of plane_k[c][t + delay[dmi][c]], over the
+ * terms with 0 <= t + delay < nsamp only; non[c] = the number of such terms; off[k][c], noff[c] the same over the two off
+ * windows together.  All i32, exact.  Zapped channels give 0 in all four.
+ * Stokes per channel, in double, each line one operation, left to right, none contracted:
+ *     m_k = on[k] / non - off[k] / noff        (two quotients, one difference)
+ *     i_c = m_AA + m_BB      q_c = m_AA - m_BB      u_c = 1.4142135623730951 m_CR      v_c = 1.4142135623730951 m_CI
+ * The sqrt 2 undoes the one that the coherence detection puts on CR and CI, so U = 2 Re(A B*) /
+ * sqrt(bpA bpB) is in the units of AA' - BB'; the quantiser's offset cancels in on minus off.
+ *     w_c = 1 where the channel is unzapped and non > 0 and noff > 0, else 0;   W = sum w_c
+ * RM synthesis.  lambda0^2 = (sum_c w_c lambda2_c) / W.  Trials phi_k = rm_lo + k rm_step, k = 0 .. nrm - 1 (doubles; nrm in
+ * 1..8192).
+ *     F[k] = (1 / W) sum_c w_c (q_c + i u_c) exp(-2 i phi_k (lambda2_c - lambda0^2))
+ * with theta = (2 phi_k) (lambda2_c - lambda0^2) (the doubling exact, one product), its sine and cosine the device
+ * library's, re += q cos + u sin, im += u cos - q sin (two products and a sum, then the accumulation), the two sums divided
+ * by W at the end.  Every sum over c is sequential in ascending c, in double.  kbest = the first k with the largest
+ * re^2 + im^2.  F is [n][nrm][2], re then im.  summary[6] per request = W, lambda0^2, mean_c i_c, mean_c v_c (over the
+ * channels with w_c = 1: the sequential sum, divided by W), |F[kbest]| = sqrt(re^2 + im^2), phi_kbest.  A request with
+ * W = 0 gets NaN for F and for summary[1..5], and kbest = -1.  The reader gets L/I = summary[4] / summary[2],
+ * V/I = summary[3] / summary[2], and the position angle at lambda0 = atan2(Im F[kbest], Re F[kbest]) / 2.
+ * What it is NOT: calibrated.  The bandpass normalisation is per hand; leakage, cross-hand delay and phase, handedness and
+ * the parallactic angle are left in; the sign of V is that of CI = Im(A conj B).  No significance of L
+ * or of the RM peak is given.
+ * tests/search_pol_ref.py restates this in NumPy; tests/test_gpu_search_pol.py holds the kernels to it (planes, images and
+ * spectra exactly; F and summary to the rounding of double worked out there).
+ * pb_search_set_pol allocates the four planes, the device staging of a host block and the device and page-locked buffers
+ * for up to max_cands requests per call; max_cands = 0 frees them and returns the search to 1-IF input.  PB_EINVAL with
+ * nothing changed for values out of range (off_len, guard, nrm as above; rm_lo, rm_step finite; max_cands >= 0), for
+ * streaming being on, or for buffers beyond 2 GiB. */
+int pb_search_set_pol(pb_search *s, int off_len, int guard, int nrm, double rm_lo, double rm_step, int max_cands);
+/* req3: n triples (dmi, t_pk, w).  Outputs (host, any may be NULL): on, off [n][4][nchan] i32; non, noff [n][nchan] i32;
+ * F [n][nrm][2] f64; kbest [n] i32; summary [n][6] f64.  Runs on the search's stream after the run it refers to; one
+ * device-to-host copy per call, through page-locked memory.  PB_EINVAL before anything is launched or written when the stage
+ * is off, no four-product block has been searched yet, n > max_cands or a request is out of range (dmi outside [0, ndm),
+ * t_pk outside [0, tout), w outside 1..64; message: pb_search_last_error). */
+int pb_search_pol(pb_search *s, const int32_t *req3, int n, int32_t *on, int32_t *non, int32_t *off, int32_t *noff, double *F,
+                  int32_t *kbest, double *summary);
+/* cands3: n triples (dmi, t_pk, tscr) as for pb_search_cutouts.  Outputs (host, either may be NULL): pft [n][4][nsub][nt],
+ * pft_hits [n][nsub][nt] u32.  Needs both cutouts and this stage switched on, n <= the smaller of their max_cands; its
+ * buffers are remade whenever either of the two set calls has changed.  Refused like pb_search_cutouts. */
+int pb_search_pol_cutouts(pb_search *s, const int32_t *cands3, int n, uint32_t *pft, uint32_t *pft_hits);
+/* plane `which` (0..3 = AA, BB, CR, CI) of the last block, [nchan][nsamp] u8, for tests; nbytes >= nchan * nsamp.
+ * pb_search_fetch_clean keeps returning xt. */
+int pb_search_pol_fetch(pb_search *s, int which, uint8_t *out, size_t nbytes);
+/* device time in ms of the last transposition into the five planes, of the last pb_search_pol's kernels, and of those
+ * kernels with the copy to the host */
+int pb_search_pol_timers(const pb_search *s, float *ms3);
+
 /* Giants and clusters of giants: the last run's S/N planes turned into candidates on the device, the step heimdall
  * takes after its matched filter (its giant finder and its labelling of giants over -cand_sep_time / -cand_sep_dm /
  * -cand_sep_filter).  heimdall's source is third-party and absent: what follows is THIS project's definition, exact,

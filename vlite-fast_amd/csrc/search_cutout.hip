@@ -182,6 +182,12 @@ __global__ __launch_bounds__(256) void k_cutout_dt(const uint32_t *__restrict__ 
     }
 }
 
+void search_cutout_ft_launch(pb_search *s, const uint8_t *plane, int n, uint32_t *ft, uint32_t *fth)
+{
+    k_cutout_ft<<<dim3(s->cut.nsub, n), 256, (size_t)s->cut.nt * sizeof(uint32_t), s->stream>>>(
+        plane, s->d_chans, s->d_delay, s->cut.d_req, s->cut.d_sub, ft, fth, s->nact, s->last_nsamp, s->cut.nt, s->tpitch);
+}
+
 #define CUT_MAX_NT 8192          // the bins of a frequency-time cutout live in LDS (4 bytes each)
 
 // One call's staging buffer, in 32-bit words: ft, ft_hits [n][nsub][nt], dt, dt_hits [n][ndmrow][nt], back to back;
@@ -263,7 +269,7 @@ extern "C" int pb_search_cutouts(pb_search *s, const int32_t *cands3, int n, uin
                                       "[0, tout) of the last run, tscr a power of two in 1..64)");
     }
     if (n == 0) return PB_OK;
-    const int nsub = s->cut.nsub, nt = s->cut.nt, nrow = s->cut.ndmrow;
+    const int nt = s->cut.nt, nrow = s->cut.ndmrow;
     const cut_layout L = cut_layout_of(s, (size_t)n);
     uint32_t *d = s->cut.d_out, *h = s->cut.h_out;
     int32_t *h_req = (int32_t *)(h + cut_layout_of(s, (size_t)s->cut.max).req);
@@ -271,8 +277,7 @@ extern "C" int pb_search_cutouts(pb_search *s, const int32_t *cands3, int n, uin
     for (int i = 0; i < 3 * n; ++i) h_req[i] = cands3[i];
     SCHK(s, hipMemcpyAsync(s->cut.d_req, h_req, (size_t)n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
     SCHK(s, hipEventRecord(s->cut.ev[0], s->stream));
-    k_cutout_ft<<<dim3(nsub, n), 256, (size_t)nt * sizeof(uint32_t), s->stream>>>(
-        s->d_xt, s->d_chans, s->d_delay, s->cut.d_req, s->cut.d_sub, d + L.ft, d + L.fth, s->nact, s->last_nsamp, nt, s->tpitch);
+    search_cutout_ft_launch(s, s->d_xt, n, d + L.ft, d + L.fth);
     k_cutout_dt<<<dim3(nrow, n), 256, 0, s->stream>>>(s->d_D, s->cut.d_req, d + L.dt, d + L.dth, s->ndm, s->last_tout, nt, s->tpitch);
     SCHK(s, hipEventRecord(s->cut.ev[1], s->stream));
     SCHK(s, hipMemcpyAsync(h, d, L.req * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));

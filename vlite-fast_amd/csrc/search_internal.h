@@ -1,6 +1,6 @@
 // What the search's translation units share on the host side: the handle, the dispersion delay, the error and timer
 // helpers, and each stage's free function.  search_run.hip holds the core (create .. fetch_clean) and the RFI cleaning;
-// search_cutout.hip, search_refine.hip, search_giants.hip and search_stream.hip one optional stage each, kernels and host side together (a
+// search_cutout.hip, search_refine.hip, search_giants.hip, search_stream.hip and search_pol.hip one optional stage each, kernels and host side together (a
 // kernel lives in the file that launches it); search_plane.hip the streaming stage's entry for fp32 planes.  Device-only helpers: search_dev.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -110,6 +110,22 @@ struct pb_search {
         hipEvent_t ev[5] = {};             // push: start, bytes on the device, appended; advance: start, end
         float ms[3] = {};                  // last push: copy, append; last advance
     } gp;
+    // polarisation (pb_search_set_pol): the blocks are [nsamp][4][nchan]; the buffers exist while it is switched on (max > 0)
+    struct {
+        int off_len = 0, guard = 0, nrm = 0, max = 0;
+        double rm_lo = 0, rm_step = 0;
+        int have = 0;                      // the planes hold the last block searched
+        uint8_t *d_codes = nullptr;        // [max_samples][4][nchan] staging of a host block
+        uint8_t *d_plane[4] = {};          // AA, BB, CR, CI: channel-major [nchan][tpitch] + the gather's pad, as d_xt
+        int32_t *d_req = nullptr;          // [max][3] requests: DM index, peak sample, on-window length
+        double *d_st = nullptr;            // [max][3][nact] q, u, lambda^2 - lambda0^2 of each unzapped channel
+        uint8_t *d_out = nullptr;          // one call's outputs (pol_layout)
+        uint8_t *h_out = nullptr;          // page-locked: the same, then the requests
+        uint32_t *d_cut = nullptr, *h_cut = nullptr;   // pb_search_pol_cutouts: pft [n][4][nsub][nt], pft_hits [n][nsub][nt]
+        int cut_sig[4] = {};               // (nsub, nt, cutouts' max_cands, max) that d_cut / h_cut were made for
+        hipEvent_t ev[3] = {};             // start, kernels done, copy done
+        float ms[2] = {};                  // last pb_search_pol: kernels, kernels + D2H copy
+    } pol;
 };
 
 // The dispersion delay of one channel in samples, in double: 4.148808e3 MHz^2 s (src/candidate.py:33) x DM x
@@ -180,6 +196,13 @@ SEARCH_LOCAL void search_cutouts_free(pb_search *s);
 SEARCH_LOCAL void search_refine_free(pb_search *s);
 SEARCH_LOCAL void search_giants_free(pb_search *s);
 SEARCH_LOCAL void search_gulp_free(pb_search *s);
+SEARCH_LOCAL void search_pol_free(pb_search *s);
+
+// search_pol.hip, for search_run.hip: the transposition of a [nsamp][4][nchan] block into the four product planes and the
+// search plane d_xt (between ev[1] and ev[2]); codes: device bytes
+SEARCH_LOCAL int search_pol_transpose(pb_search *s, const uint8_t *codes, int nsamp);
+// search_cutout.hip, for search_pol.hip: k_cutout_ft over the requests in cut.d_req on a channel-major plane laid out as d_xt
+SEARCH_LOCAL void search_cutout_ft_launch(pb_search *s, const uint8_t *plane, int n, uint32_t *ft, uint32_t *fth);
 
 // search_run.hip, for search_stream.hip: the search from the cleaning on over the nsamp samples that d_xt holds (after
 // ev[2]; `cleaned`: leave the cleaning out, the block is cleaned already), and the copies to the host that end

@@ -18,7 +18,8 @@
 // k_series_stats / k_boxcar, k_rfi_broad_list (the flagged samples) and k_rfi_broad_mask (those samples -> median).
 // The optional stages that act on what a run leaves on the device have a file each, kernels and host side together:
 // per-candidate cutouts (search_cutout.hip), a candidate's DM, width and S/N refined on a fine DM grid
-// (search_refine.hip), giants and clusters of giants (search_giants.hip).  The streaming stage (search_stream.hip)
+// (search_refine.hip), giants and clusters of giants (search_giants.hip), a candidate's Stokes spectra and rotation measure
+// (search_pol.hip, which also supplies the transposition of a four-product block).  The streaming stage (search_stream.hip)
 // stands before the cleaning instead: it fills the channel-major block piece by piece and enters at search_block.  This file is the core -- create .. destroy,
 // run / peaks, the kernels of steps 1-3 -- and the cleaning, which launches k_dedisperse .. k_boxcar for its zero-DM
 // series.  The handle and the host helpers: search_internal.h; the device helpers: search_dev.h.
@@ -577,6 +578,7 @@ extern "C" void pb_search_destroy(pb_search *s)
     search_refine_free(s);
     search_giants_free(s);
     search_gulp_free(s);
+    search_pol_free(s);
     search_release({s->d_codes, s->d_xt, s->d_delay, s->d_D, s->d_stats, s->d_snr, s->d_wid, s->d_P, s->d_peaks, s->d_chans},
                    nullptr, s->ev, 7);
     if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -697,19 +699,27 @@ static int search_run(pb_search *s, const void *codes, int codes_on_device, int 
     const int tout = nsamp - s->max_delay;
     if (tout < 64) return search_fail(s, "pb_search_run", "block shorter than the largest dispersion delay");
     SCHK(s, hipSetDevice(s->device));
-    const size_t nbytes = (size_t)nsamp * s->nchan * nbit / 8;
+    const bool pol = s->pol.max > 0;                    // the block is [nsamp][4][nchan] (pb_search_set_pol)
+    if (pol && nbit != 8) return search_fail(s, "pb_search_run", "with polarisation on the block must be 8-bit");
+    const size_t nbytes = (size_t)nsamp * s->nchan * nbit / 8 * (pol ? 4 : 1);
     const uint8_t *d_codes = (const uint8_t *)codes;
     s->gp.fill = 0;                                     // the transpose overwrites the accumulated block of the gulp stage
     s->gp.cleaned = 0;
     s->gp.tail_n = 0;
     SCHK(s, hipEventRecord(s->ev[0], s->stream));
     if (!codes_on_device) {
-        SCHK(s, hipMemcpyAsync(s->d_codes, codes, nbytes, hipMemcpyHostToDevice, s->stream));
-        d_codes = s->d_codes;
+        uint8_t *stage = pol ? s->pol.d_codes : s->d_codes;
+        SCHK(s, hipMemcpyAsync(stage, codes, nbytes, hipMemcpyHostToDevice, s->stream));
+        d_codes = stage;
     }
     SCHK(s, hipEventRecord(s->ev[1], s->stream));
-    dim3 gt((nsamp + 63) / 64, (s->nchan + 63) / 64);
-    k_transpose_codes<<<gt, 256, 0, s->stream>>>(d_codes, s->d_xt, nsamp, s->nchan, nbit, s->tpitch);
+    if (pol) {
+        const int rc = search_pol_transpose(s, d_codes, nsamp);
+        if (rc) return rc;
+    } else {
+        dim3 gt((nsamp + 63) / 64, (s->nchan + 63) / 64);
+        k_transpose_codes<<<gt, 256, 0, s->stream>>>(d_codes, s->d_xt, nsamp, s->nchan, nbit, s->tpitch);
+    }
     SCHK(s, hipEventRecord(s->ev[2], s->stream));
     return search_block(s, nsamp, thresh, want_peaks, false);
 }

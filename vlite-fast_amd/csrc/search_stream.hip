@@ -108,6 +108,7 @@ extern "C" int pb_search_set_gulp(pb_search *s, int keep_max)
     const char *fn = "pb_search_set_gulp";
     if (!s) return search_fail(s, fn, "no search handle");
     if (keep_max < 0 || keep_max > s->max_samples) return search_fail(s, fn, "keep_max must be in 0..max_samples");
+    if (keep_max > 0 && s->pol.max > 0) return search_fail(s, fn, "polarisation is switched on (pb_search_set_pol): four-product blocks are not streamed");
     SCHK(s, hipSetDevice(s->device));
     SCHK(s, hipStreamSynchronize(s->stream));
     search_gulp_free(s);

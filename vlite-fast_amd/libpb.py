@@ -59,7 +59,8 @@ EXPORTS = ["pb_config_default", "pb_create", "pb_destroy", "pb_last_error", "pb_
            "pb_search_cutouts", "pb_search_cutout_timers", "pb_search_set_refine", "pb_search_refine",
            "pb_search_refine_timers", "pb_search_set_giants", "pb_search_giants", "pb_search_giant_list",
            "pb_search_set_planes", "pb_search_giant_timers", "pb_search_set_gulp", "pb_search_push", "pb_search_push_f32", "pb_search_gulp_peaks",
-           "pb_search_gulp_run", "pb_search_gulp_advance", "pb_search_gulp_fetch", "pb_search_gulp_timers"]
+           "pb_search_gulp_run", "pb_search_gulp_advance", "pb_search_gulp_fetch", "pb_search_gulp_timers", "pb_search_set_pol",
+           "pb_search_pol", "pb_search_pol_cutouts", "pb_search_pol_fetch", "pb_search_pol_timers"]
 
 _lib = None
 
@@ -168,6 +169,11 @@ def load():
     L.pb_search_gulp_advance.argtypes = [vp, C.c_int]
     L.pb_search_gulp_fetch.argtypes = [vp, u8p, C.c_size_t, ip]
     L.pb_search_gulp_timers.argtypes = [vp, fp]
+    L.pb_search_set_pol.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]
+    L.pb_search_pol.argtypes = [vp, i32p, C.c_int, i32p, i32p, i32p, i32p, f64p, i32p, f64p]
+    L.pb_search_pol_cutouts.argtypes = [vp, i32p, C.c_int, u32p, u32p]
+    L.pb_search_pol_fetch.argtypes = [vp, C.c_int, u8p, C.c_size_t]
+    L.pb_search_pol_timers.argtypes = [vp, fp]
     for n in EXPORTS:
         f = getattr(L, n)
         if f.restype is C.c_int or n in ("pb_create", "pb_query", "pb_sync"):

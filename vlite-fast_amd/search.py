@@ -77,6 +77,7 @@ class Searcher(object):
         self._cut = None                 # (nsub, nt, ndmrow, max_cands) once set_cutouts has switched them on
         self._ref = None                 # (nstep, half_window, wmax, max_cands) once set_refine has switched it on
         self._gi = None                  # (sep_time, sep_dm, sep_filter, max_giants) once set_giants has switched it on
+        self._pol = None                 # (off_len, guard, (rm_lo, rm_step, nrm), max_cands) once set_pol has switched it on
         self.dms = dm_min + dm_step * np.arange(self.ndm) if dm_list is None else np.asarray(dm_list, np.float64)
         self._nsamp = 0
         self._tout = 0
@@ -165,6 +166,75 @@ class Searcher(object):
         t = (C.c_float * 2)()
         self._L.pb_search_cutout_timers(self._s, t)
         return dict(kernels=float(t[0]), with_copy=float(t[1]))
+
+    def set_pol(self, off_len=64, guard=8, rm=(-2000.0, 2.0, 2001), max_cands=32):
+        """polarisation of candidates (include/pb_hip.h, pb_search_set_pol): from now on run() and peaks() take blocks of
+        [nsamp][4][nchan] 8-bit codes (AA, BB, CR, CI: a nifs 4 filterbank's rows) and search the rounded mean of AA and
+        BB; pol() then gives on- and off-pulse spectra (off windows of off_len samples, guard samples away from the on
+        window) and an RM synthesis over the trials rm = (first, step, how many), up to max_cands requests per call.
+        max_cands=0 switches it off and returns the search to 1-IF blocks."""
+        lo, step, nrm = float(rm[0]), float(rm[1]), int(rm[2])
+        rc = self._L.pb_search_set_pol(self._s, int(off_len), int(guard), nrm, lo, step, int(max_cands))
+        self._check(rc, None, ValueError)
+        self._pol = (int(off_len), int(guard), (lo, step, nrm), int(max_cands)) if max_cands else None
+
+    def _nif(self):
+        """rows of nchan codes per time sample of a block: 4 with polarisation on"""
+        return 4 if self._pol is not None else 1
+
+    def pol(self, dmi, t, w):
+        """pb_search_pol on the last block searched, one request per element (scalars or equally long sequences): trial-DM
+        index, peak sample in block coordinates, on-window length w in 1..64.  Returns dict(on, off [n][4][nchan] i32, non,
+        noff [n][nchan] i32, F [n][nrm][2] f64 (re, im), kbest [n], summary [n][6] = W, lambda0^2, mean i, mean v,
+        |F[kbest]|, RM of kbest; rms [nrm] the trial grid, freqs [nchan] in MHz)."""
+        if self._pol is None:
+            raise self._lp.PbError("polarisation is not switched on: call set_pol() first")
+        lo, step, nrm = self._pol[2]
+        req = np.stack(np.broadcast_arrays(np.atleast_1d(dmi), np.atleast_1d(t), np.atleast_1d(w)), axis=1)
+        req = np.ascontiguousarray(req, np.int32)
+        n = req.shape[0]
+        out = dict(on=np.zeros((n, 4, self.nchan), np.int32), non=np.zeros((n, self.nchan), np.int32),
+                   off=np.zeros((n, 4, self.nchan), np.int32), noff=np.zeros((n, self.nchan), np.int32),
+                   F=np.full((n, nrm, 2), np.nan), kbest=np.full(n, -1, np.int32), summary=np.full((n, 6), np.nan))
+        i32p, f64p = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        rc = self._L.pb_search_pol(self._s, req.ctypes.data_as(i32p), n, out["on"].ctypes.data_as(i32p),
+                                   out["non"].ctypes.data_as(i32p), out["off"].ctypes.data_as(i32p),
+                                   out["noff"].ctypes.data_as(i32p), out["F"].ctypes.data_as(f64p),
+                                   out["kbest"].ctypes.data_as(i32p), out["summary"].ctypes.data_as(f64p))
+        self._check(rc, "pb_search_pol")
+        out["rms"] = lo + step * np.arange(nrm)
+        out["freqs"] = float(np.float32(self.fch1)) + float(np.float32(self.foff)) * np.arange(self.nchan)
+        return out
+
+    def pol_cutouts(self, dmi, t, tscr):
+        """the four products' frequency-time images of the last block (set_cutouts() and set_pol() both on), requests as
+        for cutouts(): dict(pft [n][4][nsub][nt] u32, pft_hits [n][nsub][nt] u32)"""
+        if self._pol is None or self._cut is None:
+            raise self._lp.PbError("pol_cutouts needs set_cutouts() and set_pol()")
+        nsub, nt, _, _ = self._cut
+        req = np.stack(np.broadcast_arrays(np.atleast_1d(dmi), np.atleast_1d(t), np.atleast_1d(tscr)), axis=1)
+        req = np.ascontiguousarray(req, np.int32)
+        n = req.shape[0]
+        out = dict(pft=np.zeros((n, 4, nsub, nt), np.uint32), pft_hits=np.zeros((n, nsub, nt), np.uint32))
+        u32p = C.POINTER(C.c_uint32)
+        rc = self._L.pb_search_pol_cutouts(self._s, req.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                                           out["pft"].ctypes.data_as(u32p), out["pft_hits"].ctypes.data_as(u32p))
+        self._check(rc, "pb_search_pol_cutouts")
+        return out
+
+    def pol_fetch(self, which):
+        """plane `which` (0..3 = AA, BB, CR, CI) of the last block, [nchan][nsamp] u8 as the file held it"""
+        out = np.empty((self.nchan, self._nsamp), np.uint8)
+        rc = self._L.pb_search_pol_fetch(self._s, int(which), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.nbytes)
+        self._check(rc, "pb_search_pol_fetch")
+        return out
+
+    def pol_timers(self):
+        """device ms of the last transposition into the five planes, of the last pol() call's kernels, and of those with
+        the copy to the host"""
+        t = (C.c_float * 3)()
+        self._L.pb_search_pol_timers(self._s, t)
+        return dict(transpose=float(t[0]), kernels=float(t[1]), with_copy=float(t[2]))
 
     def set_refine(self, nstep=32, half_window=128, wmax=32, max_cands=32):
         """refinement of candidates on the last block (include/pb_hip.h, pb_search_set_refine): nstep fine trial DMs per
@@ -324,7 +394,7 @@ class Searcher(object):
         are already on the GPU (e.g. PbHandle.output_dev)."""
         if device_ptr is None:
             codes = np.ascontiguousarray(codes, np.uint8).ravel()
-            nsamp = codes.size * (8 // nbit) // self.nchan
+            nsamp = codes.size * (8 // nbit) // (self.nchan * self._nif())
             ptr, on_dev = codes.ctypes.data_as(C.c_void_p), 0
         else:
             if nsamp is None:
@@ -452,13 +522,14 @@ class Searcher(object):
         return dict(copy=float(t[0]), append=float(t[1]), advance=float(t[2]))
 
     def run(self, codes, nbit=8, want_series=False, device_ptr=None, nsamp=None):
-        """codes: uint8 array holding nsamp x nchan samples of nbit bits (SIGPROC order), or device_ptr + nsamp for
+        """codes: uint8 array holding nsamp x nchan samples of nbit bits (SIGPROC order; with set_pol() on nsamp x 4 x nchan
+        8-bit codes, and nsamp counts 4 nchan bytes per sample), or device_ptr + nsamp for
         codes that are already on the GPU (e.g. PbHandle.output_dev; the contract is under pb_search_run in
         include/pb_hip.h: the producer's stream synchronised, any byte address, valid until this returns).
         Returns dict(snr [ndm][tout] f32, width_log2 [ndm][tout] u8, stats [ndm][2], series?)."""
         if device_ptr is None:
             codes = np.ascontiguousarray(codes, np.uint8).ravel()
-            nsamp = codes.size * (8 // nbit) // self.nchan
+            nsamp = codes.size * (8 // nbit) // (self.nchan * self._nif())
             ptr, on_dev = codes.ctypes.data_as(C.c_void_p), 0
         else:
             if nsamp is None:
@@ -609,11 +680,24 @@ class GulpSearch(object):
     device.  feed(p1) .. feed(pk) + finish() return, in order, the candidates of push(b1) .. push(bm) + finish() over
     the same stream cut into blocks of N, the remainder last (tests/test_gpu_search_stream.py).  feed_plane() takes a
     piece as an fp32 plane instead, quantised to 8 bits on the device (Searcher.push_plane), and may alternate with
-    feed().  gulp=None (default): push() only."""
+    feed().  gulp=None (default): push() only.
+    pol=dict(thresh=..., max_per_gulp=...) (the searcher's set_pol() must be on; push() only, not with gulp=N): the blocks
+    are [nsamp][4 nchan] (AA, BB, CR, CI rows per sample) and the same selection gets a "pol" entry -- the candidate's slice
+    of Searcher.pol for the request (dmi, peak in block coordinates, min(2^tfilt, 64)): on, non, off, noff, F, kbest, summary,
+    rms, freqs; with cutouts also on the strongest of them, as many as the cutouts' max_cands, also carry pft, pft_hits and
+    tscr of Searcher.pol_cutouts.  feed() and feed_plane() raise."""
 
     def __init__(self, searcher, threshold=6.0, nbit=8, coincidencer=None, utc_start="1970-01-01-00:00:00", beam=1,
-                 cutouts=None, refine=None, giants=None, gulp=None):
+                 cutouts=None, refine=None, giants=None, gulp=None, pol=None):
         self.s, self.threshold, self.nbit = searcher, threshold, nbit
+        self.pol = None
+        if pol is not None:
+            if searcher._pol is None:
+                raise ValueError("GulpSearch(pol=...): call the searcher's set_pol() first")
+            if gulp is not None:
+                raise ValueError("GulpSearch(pol=...): four-product blocks are not streamed (gulp=N)")
+            self.pol = (float(pol.get("thresh", threshold)), min(int(pol.get("max_per_gulp", 32)), searcher._pol[3]))
+        self.nif = searcher._nif()
         self.gulp = None
         if gulp is not None:
             if int(gulp) < 1:
@@ -635,7 +719,7 @@ class GulpSearch(object):
                 raise ValueError("GulpSearch(cutouts=...): call the searcher's set_cutouts() first")
             self.cut = (float(cutouts.get("thresh", threshold)), min(int(cutouts.get("max_per_gulp", 32)), searcher._cut[3]))
         self.last_first = 0              # stream index of the first sample of the latest push()'s / finish()'s batch
-        self.tail = np.zeros((0, searcher.nchan), np.uint8)
+        self.tail = np.zeros((0, self.nif * searcher.nchan), np.uint8)
         self.done = 0                    # output samples produced so far = stream index of the next block's first output
         self.ov = (1 << (searcher.nbox - 1)) - 1        # widest boxcar - 1
         self.pending = None              # peaks of the latest gulp's last `ov` output samples (for finish())
@@ -677,6 +761,26 @@ class GulpSearch(object):
         for c, e in zip(sel, r):
             c["refined"] = None if e is None else dict(e, peak=e["peak"] + sample0)
 
+    def _pol(self, cands, sample0):
+        """attach the polarisation products to the strongest candidates; sample0 as in _cutouts"""
+        if self.pol is None:
+            return
+        thresh, most = self.pol
+        sel = [c for c in cands if c["snr"] >= thresh][:most]
+        if not sel:
+            return
+        dmi, tpk = [c["dmi"] for c in sel], [c["peak_idx"] - sample0 for c in sel]
+        r = self.s.pol(dmi, tpk, [min(1 << c["tfilt"], 64) for c in sel])
+        for i, c in enumerate(sel):
+            c["pol"] = dict({k: r[k][i] for k in POL_KEYS}, rms=r["rms"], freqs=r["freqs"])
+        if self.s._cut is not None:
+            # the images of as many of them, strongest first, as the cutouts' max_cands allows
+            ncut = min(len(sel), self.s._cut[3])
+            tscr = [max(1, (1 << c["tfilt"]) // 2) for c in sel[:ncut]]
+            pc = self.s.pol_cutouts(dmi[:ncut], tpk[:ncut], tscr)
+            for i, c in enumerate(sel[:ncut]):
+                c["pol"].update(pft=pc["pft"][i], pft_hits=pc["pft_hits"][i], tscr=tscr[i])
+
     def _giants(self, t_lo, t_hi, sample0):
         """the candidates of the current block's samples [t_lo, t_hi) from the device's giants"""
         res = self.s.giants(self.threshold, t_lo, t_hi)
@@ -692,10 +796,10 @@ class GulpSearch(object):
         return dict(dmi=pk["dmi"][sel], t=pk["t"][sel], snr=pk["snr"][sel], width_log2=pk["width_log2"][sel])
 
     def push(self, block):
-        """block: uint8 [nsamp][nchan] (8-bit codes) of NEW samples"""
+        """block: uint8 [nsamp][nchan] (8-bit codes) of NEW samples; [nsamp][4 nchan] with the searcher's set_pol() on"""
         if self.nbit != 8:
             raise ValueError("GulpSearch takes unpacked 8-bit samples")
-        block = np.asarray(block, np.uint8).reshape(-1, self.s.nchan)
+        block = np.asarray(block, np.uint8).reshape(-1, self.nif * self.s.nchan)
         data = np.concatenate([self.tail, block]) if self.tail.size else block
         if data.shape[0] - self.s.max_delay < 64 + self.ov:
             self.tail = data                          # not enough yet for one output block
@@ -724,6 +828,7 @@ class GulpSearch(object):
         first = self.last_first = self.done
         self._cutouts(cands, first)
         self._refine(cands, first)
+        self._pol(cands, first)
         self.done += nout
         return cands, first, nout
 
@@ -746,8 +851,8 @@ class GulpSearch(object):
         """GulpSearch(gulp=N): a piece of the stream, any number of samples of nbit bits in SIGPROC order -- a host uint8
         array (packed as in a file), or device_ptr + nsamp for bytes on the GPU (Searcher.run's contract).  Returns the
         candidates of the gulps that the piece completed (often none)."""
-        if self.gulp is None:
-            raise ValueError("feed() needs GulpSearch(gulp=N)")
+        if self.gulp is None or self.nif != 1:
+            raise ValueError("feed() needs GulpSearch(gulp=N), and a searcher without set_pol()")
         nchan = self.s.nchan
         if nbit not in (8, 4, 2) or (nchan * nbit) % 8:
             raise ValueError("feed: nbit 8, 4 or 2, and a time sample must fill whole bytes (nchan x nbit a multiple of 8)")
@@ -768,8 +873,8 @@ class GulpSearch(object):
         """feed() for a piece of an fp32 plane [nsamp][nchan] (Searcher.push_plane: quantised to 8 bits on the device) --
         a host float32 array, or device_ptr + nsamp.  The same cuts, fires and returns; feed() and feed_plane() may
         alternate on one stream."""
-        if self.gulp is None:
-            raise ValueError("feed_plane() needs GulpSearch(gulp=N)")
+        if self.gulp is None or self.nif != 1:
+            raise ValueError("feed_plane() needs GulpSearch(gulp=N), and a searcher without set_pol()")
         nchan = self.s.nchan
         if device_ptr is None:
             plane = np.ascontiguousarray(plane, np.float32).ravel()
@@ -813,6 +918,7 @@ class GulpSearch(object):
             cands = candidates_from_peaks(pk, self.s.dms, self.s.tsamp, sample0=sample0)
         self._cutouts(cands, sample0)
         self._refine(cands, sample0)
+        self._pol(cands, sample0)
         return cands
 
     def _finish(self):
@@ -838,7 +944,10 @@ def arg_parser(with_file=True):
     """the command line of main(): heimdall's flag names.  with_file=False: the flags that a host which feeds the search
     itself accepts (process_baseband --search) -- the same ones less -f and -stream_chunk."""
     import argparse
-    ap = argparse.ArgumentParser(prog="search" if with_file else "--search", prefix_chars="-")
+    ap = argparse.ArgumentParser(prog="search" if with_file else "--search", prefix_chars="-",
+                                 epilog="with -f also: -pol [-pol_thresh S] [-pol_max N] [-rm LO HI] [-rm_step D] [-pol_off L G]: "
+                                        "a nifs 4 filterbank (AA, BB, CR, CI); Stokes spectra and RM synthesis of the strongest "
+                                        "candidates (pol_parser)")
     if with_file:
         ap.add_argument("-f", dest="fil", required=True)
     ap.add_argument("-dm", nargs=2, type=float, default=list(HEIMDALL_DM))
@@ -873,17 +982,36 @@ def arg_parser(with_file=True):
     return ap
 
 
+def pol_parser():
+    """the flags of -pol, parsed apart from arg_parser()'s: a command line without -pol gives the namespace it always gave"""
+    import argparse
+    ap = argparse.ArgumentParser(prog="search", prefix_chars="-", add_help=False, allow_abbrev=False)
+    ap.add_argument("-pol", action="store_true", help="a nifs 4 filterbank (AA, BB, CR, CI): search total intensity; Stokes spectra and RM synthesis of the strongest candidates; with -output_dir a .pol and a .pol.npz file beside each .cand")
+    ap.add_argument("-pol_thresh", type=float, default=None, help="with -pol: lowest S/N analysed (default: -detect_thresh)")
+    ap.add_argument("-pol_max", type=int, default=32, help="with -pol: most candidates analysed per gulp")
+    ap.add_argument("-rm", nargs=2, type=float, default=[-2000.0, 2000.0], help="with -pol: first and last trial RM in rad/m^2")
+    ap.add_argument("-rm_step", type=float, default=2.0, help="with -pol: step of the trial RMs")
+    ap.add_argument("-pol_off", nargs=2, type=int, default=[64, 8], help="with -pol: length of each off-pulse window and its guard from the on window, in samples")
+    return ap
+
+
 def parse_flags(flags):
     """process_baseband's --search "<flags>": the string split as a shell would and parsed by the search's own parser
-    (arg_parser(with_file=False) and parse_args' checks); an unknown flag, -f or -stream_chunk ends in SystemExit"""
+    (arg_parser(with_file=False) and parse_args' checks); an unknown flag, -f, -stream_chunk or -pol ends in SystemExit"""
     import shlex
     return parse_args(shlex.split(flags), with_file=False)
 
 
 def parse_args(argv=None, with_file=True):
     """arg_parser() plus the checks between flags"""
+    import sys
     ap = arg_parser(with_file)
-    a = ap.parse_args(argv)
+    argv = sys.argv[1:] if argv is None else list(argv)
+    pa, rest = pol_parser().parse_known_args(argv)
+    a = ap.parse_args(rest)
+    alone = [f for f in ("-pol_thresh", "-pol_max", "-rm", "-rm_step", "-pol_off") if f in argv]
+    if alone and not pa.pol:
+        ap.error("%s: only with -pol" % ", ".join(alone))
     if a.cutouts and not a.output_dir:
         ap.error("-cutouts needs -output_dir")
     if a.cutout_max < 1:
@@ -902,7 +1030,70 @@ def parse_args(argv=None, with_file=True):
         ap.error("-max_giants must be in 1..4194304")
     if with_file and a.stream_chunk < 0:
         ap.error("-stream_chunk must be >= 0")
+    if pa.pol:
+        if not with_file:
+            ap.error("-pol reads a nifs 4 file: a host that feeds the search itself feeds it one IF")
+        if a.stream_chunk:
+            ap.error("-pol reads whole gulps: not with -stream_chunk")
+        if pa.pol_thresh is None:
+            pa.pol_thresh = a.detect_thresh
+        if pa.pol_max < 1:
+            ap.error("-pol_max must be >= 1")
+        if not pa.rm_step > 0 or pa.rm[1] < pa.rm[0] or rm_trials(pa.rm[0], pa.rm[1], pa.rm_step) > 8192:
+            ap.error("-rm LO HI with LO <= HI and -rm_step > 0, at most 8192 trials")
+        if not (1 <= pa.pol_off[0] <= 1024 and 0 <= pa.pol_off[1] <= 1024):
+            ap.error("-pol_off L G: L in 1..1024, G in 0..1024")
+        for k, v in vars(pa).items():               # (only with -pol: without it the namespace is what it always was)
+            setattr(a, k, v)
     return a
+
+
+def rm_trials(lo, hi, step):
+    """how many trial RMs lo, lo + step, .. reach hi (a step that falls 1e-9 of itself short of hi still counts)"""
+    return int(np.floor((hi - lo) / step + 1e-9)) + 1
+
+
+POL_KEYS = ("on", "non", "off", "noff", "F", "kbest", "summary")
+
+
+def pol_numbers(p):
+    """a candidate's "pol" entry -> (RM of the synthesis peak, L/I, V/I, position angle at lambda0 in degrees);
+    uncalibrated (include/pb_hip.h, pb_search_set_pol), NaN where no channel had both windows"""
+    k, sm = int(p["kbest"]), p["summary"]
+    if k < 0:
+        return (float("nan"),) * 4
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (float(sm[5]), float(sm[4] / sm[2]), float(sm[3] / sm[2]),
+                float(np.degrees(0.5 * np.arctan2(p["F"][k, 1], p["F"][k, 0]))))
+
+
+def pol_line(c):
+    """a candidate's line followed by the RM of its synthesis peak, L/I, V/I and the position angle in degrees"""
+    return "%s\t%.4f\t%.4f\t%.4f\t%.3f" % ((candidate_line(c),) + pol_numbers(c["pol"]))
+
+
+def write_pol(path, cands, tsamp):
+    """The polarised candidates of one gulp (those that carry a "pol" entry): path gets one pol_line each, path + ".npz"
+    F, rms, on, non, off, noff, summary, kbest, freqs (pft, pft_hits, tscr of the first of them that were cut out too) and the candidates'
+    nine columns as `cands` [n][9].  Returns how many were written (0: no files)."""
+    cc = [c for c in cands if "pol" in c]
+    if not cc:
+        return 0
+    with open(path, "w") as f:
+        f.write("".join(pol_line(c) + "\n" for c in cc))
+    d = {k: np.stack([c["pol"][k] for c in cc]) for k in POL_KEYS}
+    d["rms"], d["freqs"] = cc[0]["pol"]["rms"], cc[0]["pol"]["freqs"]
+    cp = [c for c in cc if "pft" in c["pol"]]       # the first of them: the images stop at the cutouts' max_cands
+    if cp:
+        for k in ("pft", "pft_hits"):
+            d[k] = np.stack([c["pol"][k] for c in cp])
+        d["tscr"] = np.array([c["pol"]["tscr"] for c in cp], np.int32)
+    d["cands"] = np.array([[c["snr"], c["peak_idx"], c["peak_time"], c["tfilt"], c["dmi"], c["dm"], c["ngiant"], c["i0"], c["i1"]]
+                           for c in cc], np.float64)
+    d["tsamp"] = np.float64(tsamp)
+    with open(path + ".npz", "wb") as f:
+        np.savez(f, **d)
+    return len(cc)
 
 
 CUTOUT_KEYS = ("ft", "ft_hits", "dt", "dt_hits", "dm_rows")
@@ -987,10 +1178,15 @@ def open_search(a, hdr, gulp, device=None, searcher=None):
         # the default geometry; a shorter window where the blocks are too short for two of the default
         s.set_refine(half_window=max(64, min(128, (maxs // 4) & ~1)), max_cands=a.refine_max)
         ref = dict(thresh=a.refine_thresh, max_per_gulp=a.refine_max)
+    pol = None
+    if getattr(a, "pol", False):
+        s.set_pol(off_len=a.pol_off[0], guard=a.pol_off[1], rm=(a.rm[0], a.rm_step, rm_trials(a.rm[0], a.rm[1], a.rm_step)),
+                  max_cands=a.pol_max)
+        pol = dict(thresh=a.pol_thresh, max_per_gulp=a.pol_max)
     gi = dict(sep_time=a.cand_sep_time, sep_dm=a.cand_sep_dm, sep_filter=a.cand_sep_filter,
               max_giants=a.max_giants) if a.giants else None
     g = GulpSearch(s, threshold=a.detect_thresh, coincidencer=a.coincidencer, utc_start=utc, beam=a.beam, cutouts=cut,
-                   refine=ref, giants=gi, gulp=gulp)
+                   refine=ref, giants=gi, gulp=gulp, pol=pol)
     if a.output_dir:
         os.makedirs(a.output_dir, exist_ok=True)
     stems = set()
@@ -1009,6 +1205,8 @@ def open_search(a, hdr, gulp, device=None, searcher=None):
                 write_cutouts_npz(os.path.join(a.output_dir, stem + ".cutouts.npz"), cands, tsamp)
             if a.refine:
                 write_refined(os.path.join(a.output_dir, stem + ".refined"), cands)
+            if pol:
+                write_pol(os.path.join(a.output_dir, stem + ".pol"), cands, tsamp)
         return len(cands)
 
     return s, g, emit
@@ -1024,21 +1222,30 @@ def main(argv=None):
     -refine a .refined file (the refined candidates' lines, each followed by refined DM, S/N, width and peak sample).
     -giants takes the candidates from the GPU's giants and clusters (heimdall's -cand_sep_time / -cand_sep_dm /
     -cand_sep_filter; this project's own definition) instead of the host's grouping of the point list.
+    -pol takes a nifs 4 file (process_baseband -P 2 --coherence: AA, BB, CR, CI), searches its total intensity and gives
+    the strongest candidates of each gulp Stokes spectra and an RM synthesis (-rm, -rm_step, -pol_off; uncalibrated:
+    include/pb_hip.h, pb_search_set_pol); with -output_dir a .pol file (each line followed by RM, L/I, V/I, position angle
+    in degrees) and a .pol.npz beside each .cand.
     -stream_chunk M reads the file in pieces of M samples and feeds them to GulpSearch(gulp=-nsamps_gulp): the same
     lines, gathered on the GPU as a host behind pb_process would gather them; on this path 4- and 2-bit files are
     accepted and fed packed."""
     sig = importlib.import_module(_pkg + ".sigproc")
     a = parse_args(argv)
+    use_pol = getattr(a, "pol", False)
     with open(a.fil, "rb") as f:
         hdr, off = sig.read_header(f.read(4096))
     nbits = hdr["nbits"]
     if a.stream_chunk:
         if nbits not in (8, 4, 2) or hdr.get("nifs", 1) != 1 or (hdr["nchans"] * nbits) % 8:
             raise SystemExit("search -stream_chunk: 8-, 4- or 2-bit single-IF filterbanks whose time samples fill whole bytes only")
+    elif use_pol:
+        if nbits != 8 or hdr.get("nifs", 1) != 4:
+            raise SystemExit("search -pol: 8-bit filterbanks with nifs 4 (AA, BB, CR, CI) only")
     elif nbits != 8 or hdr.get("nifs", 1) != 1:
         raise SystemExit("search: 8-bit single-IF filterbanks only")
     s, g, emit = open_search(a, hdr, a.nsamps_gulp if a.stream_chunk else None)
     nchan, ntot = hdr["nchans"], 0
+    nrow = nchan * (4 if use_pol else 1)              # bytes of a time sample on the whole-gulp path
 
     with open(a.fil, "rb") as f:
         f.seek(off)
@@ -1050,10 +1257,10 @@ def main(argv=None):
                 break
             ntot += emit(g.feed(blk[:blk.size // rowb * rowb], nbit=nbits))
         while not a.stream_chunk:
-            blk = np.frombuffer(f.read(a.nsamps_gulp * nchan), np.uint8)
-            if blk.size < nchan:
+            blk = np.frombuffer(f.read(a.nsamps_gulp * nrow), np.uint8)
+            if blk.size < nrow:
                 break
-            ntot += emit(g.push(blk[:blk.size // nchan * nchan].reshape(-1, nchan)))
+            ntot += emit(g.push(blk[:blk.size // nrow * nrow].reshape(-1, nrow)))
     ntot += emit(g.finish())
     s.close()
     return ntot
