@@ -681,6 +681,61 @@ int pb_search_gulp_advance(pb_search *s, int keep);
 int pb_search_gulp_fetch(pb_search *s, uint8_t *xt, size_t nbytes, int *fill);
 int pb_search_gulp_timers(const pb_search *s, float *ms3);
 
+/* Sub-band search: band-limited bursts.  The search sums every unzapped channel before it looks for a pulse, so a burst
+ * that lives in a quarter of the band reaches half the S/N it has in its own quarter and may never cross the threshold.
+ * This stage searches runs of base sub-bands of the block that the last search left on the device and reports the cells
+ * where a band beats the full band.  heimdall has no such stage: the definition is THIS project's own.  Off until
+ * pb_search_set_subbands; a pb_search on which it was never called allocates nothing more, launches nothing more and
+ * returns what it returns without it, byte for byte.  Not combined with pb_search_set_pol.
+ * Notation: xt[c][t], delay[d][c], tout, the unzapped channels chans[] as under pb_search_set_cutouts; snr[d][t] the
+ * full-band S/N planes on the device.
+ *   1. Base sub-bands.  nsb of them, nsb in {2, 4, 8, 16}, nchan % nsb == 0.  Sub-band s is the unzapped channels with index
+ *      in [s nchan/nsb, (s+1) nchan/nsb): the cutouts' convention, one run [first, last) of chans[]; it may be empty.
+ *   2. Bands.  A band is a run of base sub-bands (first, count), count >= 1, first + count <= nsb.  This ABI takes an explicit
+ *      list of nbands <= 64 of them, each with count < nsb (the whole band is the ordinary search and is refused).
+ *      search.py's subband_list(nsb) makes the default, staggered dyadic, widest first: for c = nsb/2, nsb/4, .. 1 the bands
+ *      (k max(c/2, 1), c), k = 0, 1, .. while they fit -- 2, 7, 18, 41 bands for nsb 2, 4, 8, 16.  The half-step stagger
+ *      matters: a burst over the middle half of the band gains nothing from either aligned half.
+ *   3. Sub-band series.  S[s][d][t] = sum over the channels c of sub-band s of xt[c][t + delay[d][c]], t in [0, tout): xt as
+ *      the last search left it (cleaned in place if cleaning is on; the accumulated gulp when streaming), the main delay
+ *      table, the last search's tout.  Exact u32; sum over s of S[s][d][t] == D[d][t], the search's own series.
+ *   4. Band series.  B[b][d][t] = sum over the sub-bands s of band b of S[s][d][t].
+ *   5. Band statistics.  Each band series gets its level, clipped rms, running baseline, S/N and log2-width plane by the
+ *      text under pb_search_set_baseline, with the handle's baseline window and boxcars -- by the search's own kernels on
+ *      the band rows, so a band's planes are bit for bit those of pb_search_run on a handle with everything outside the
+ *      band zapped (and the same tout).  A band with no unzapped channel, or with rms not above 0, has S/N 0 everywhere.
+ *   6. Best band per (d, t): the band with the largest S/N, compared in binary32; ties go to the smallest band index (-0
+ *      equals +0); a NaN never wins (if every band's is a NaN the cell keeps band 0's).  Its S/N, log2 width and index are
+ *      the cell's sub-band values.
+ *   7. Points.  A cell is reported when t_lo <= t < t_hi, best S/N >= thresh, and best S/N > snr[d][t], all compared in
+ *      binary32 (a NaN on either side reports nothing).  The last test keeps a broadband pulse from coming back once per
+ *      band.  A point is PB_SUBPOINT_WORDS int32: dmi, t, S/N bits, log2 width, band index, full-band S/N bits.
+ *   8. Point list.  Its order is unspecified (the host sorts it); *npoints is the exact count; when it exceeds the capacity
+ *      (the smaller of max_points and max_out) the list is incomplete and *overflow = 1.
+ *   9. DM chunks.  The trial DMs are processed dm_chunk rows at a time so that the stage's memory is bounded: dm_chunk = 0
+ *      means the largest multiple of 4 that keeps the stage's buffers within 1 GiB, at least 4; any value is cut to ndm and
+ *      to 65535 / nbands (the band rows of a pass are one grid dimension).  Results do not depend on dm_chunk.
+ * Only exact integer sums and binary32 comparisons are new; tests/search_subband_ref.py restates them and
+ * tests/test_gpu_search_subband.py holds the kernels to them exactly.
+ * pb_search_set_subbands allocates the buffers; nbands = 0 frees them and switches the stage off.  PB_EINVAL with nothing
+ * changed for a bad nsb, a bad band list, dm_chunk < 0, max_points outside 1..2^26, or polarisation being on. */
+#define PB_SUBPOINT_WORDS 6
+int pb_search_set_subbands(pb_search *s, int nsb, const int32_t *bands2, int nbands, int dm_chunk, int max_points);
+/* On the block and planes of the last pb_search_run / pb_search_peaks / pb_search_gulp_*: points (host) receives
+ * min(*npoints, max_out, max_points) points.  PB_EINVAL with a message (pb_search_last_error), nothing launched or written,
+ * when the stage is off, no block has been searched, the planes were replaced by pb_search_set_planes (their tout is not the
+ * last search's), the range is not 0 <= t_lo < t_hi <= tout, the threshold is a NaN, an output pointer is missing or
+ * polarisation is on. */
+int pb_search_subbands(pb_search *s, float thresh, int t_lo, int t_hi, int32_t *points, int max_out, int *npoints, int *overflow);
+/* One trial DM of the current block recomputed through the same kernels, for tests and diagnostics.  Outputs (host, any may
+ * be NULL): sub [nsb][tout] u32; band_snr [nbands][tout], band_wid [nbands][tout], band_stats [nbands][2]; best_snr,
+ * best_wid, best_band [tout]. */
+int pb_search_subband_dm(pb_search *s, int dmi, uint32_t *sub, float *band_snr, uint8_t *band_wid, float *band_stats,
+                         float *best_snr, uint8_t *best_wid, uint8_t *best_band);
+/* the last pb_search_subbands: device time in ms of the sub-band dedispersion, of the band sums, prefix sums and statistics,
+ * of the boxcars and the best band (each added up over the chunks), and of everything with the copy to the host */
+int pb_search_subband_timers(const pb_search *s, float *ms4);
+
 /* Page-locked host memory for the blocks handed to pb_submit_vdif(_at) (H2D copies from pageable memory are
  * staged and synchronous); the reference allocates its 1-s host buffer the same way (cudaMallocHost,
  * src/process_baseband.cu:579).  A host program above this ABI needs no HIP headers.  NULL on failure. */

@@ -202,6 +202,21 @@ static cut_layout cut_layout_of(const pb_search *s, size_t n)
     return {nf, nd, 0, nf, 2 * nf, 2 * nf + nd, 2 * (nf + nd), 2 * (nf + nd) + 3 * n};
 }
 
+int search_sub_runs(pb_search *s, int nsub, std::vector<int32_t> &run)
+{
+    std::vector<int32_t> chans(s->nact);
+    run.assign(2 * (size_t)nsub, 0);
+    SCHK(s, hipMemcpy(chans.data(), s->d_chans, chans.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    const int per = s->nchan / nsub;
+    int k = 0;
+    for (int b = 0; b < nsub; ++b) {
+        run[2 * b] = k;
+        while (k < s->nact && chans[k] < (b + 1) * per) ++k;
+        run[2 * b + 1] = k;
+    }
+    return PB_OK;
+}
+
 void search_cutouts_free(pb_search *s)
 {
     search_release({s->cut.d_req, s->cut.d_sub, s->cut.d_out}, s->cut.h_out, s->cut.ev, 3);
@@ -225,16 +240,8 @@ extern "C" int pb_search_set_cutouts(pb_search *s, int nsub, int nt, int ndmrow,
     SCHK(s, hipStreamSynchronize(s->stream));
     search_cutouts_free(s);
     if (max_cands == 0) return PB_OK;
-    // zapped channels are left out of chans[], so a subband's channels are one run of it
-    std::vector<int32_t> chans(s->nact), run(2 * (size_t)nsub);
-    SCHK(s, hipMemcpy(chans.data(), s->d_chans, chans.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    const int per = s->nchan / nsub;
-    int k = 0;
-    for (int b = 0; b < nsub; ++b) {
-        run[2 * b] = k;
-        while (k < s->nact && chans[k] < (b + 1) * per) ++k;
-        run[2 * b + 1] = k;
-    }
+    std::vector<int32_t> run;
+    if (int rc = search_sub_runs(s, nsub, run)) return rc;
     s->cut.nsub = nsub;
     s->cut.nt = nt;
     s->cut.ndmrow = ndmrow;

@@ -1,6 +1,6 @@
 // What the search's translation units share on the host side: the handle, the dispersion delay, the error and timer
 // helpers, and each stage's free function.  search_run.hip holds the core (create .. fetch_clean) and the RFI cleaning;
-// search_cutout.hip, search_refine.hip, search_giants.hip, search_stream.hip and search_pol.hip one optional stage each, kernels and host side together (a
+// search_cutout.hip, search_refine.hip, search_giants.hip, search_stream.hip, search_pol.hip and search_subband.hip one optional stage each, kernels and host side together (a
 // kernel lives in the file that launches it); search_plane.hip the streaming stage's entry for fp32 planes.  Device-only helpers: search_dev.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -126,6 +126,23 @@ struct pb_search {
         hipEvent_t ev[3] = {};             // start, kernels done, copy done
         float ms[2] = {};                  // last pb_search_pol: kernels, kernels + D2H copy
     } pol;
+    // sub-band search (pb_search_set_subbands); the buffers exist while it is switched on (nbands > 0)
+    struct {
+        int nsb = 0, nbands = 0, max = 0;
+        int chunk = 0;                     // trial DMs per pass of the stage's kernels
+        int32_t *d_run = nullptr;          // [nsb][2] each base sub-band's run [first, last) of chans[]
+        int32_t *d_bands = nullptr;        // [nbands][2] first base sub-band, how many
+        uint32_t *d_S = nullptr;           // [nsb][rows][tpitch] sub-band series of a pass's rows
+        uint32_t *d_B = nullptr;           // [nbands][rows][tpitch] band series; the next four are laid out the same
+        uint64_t *d_P = nullptr;           // prefix sums, pitch ppitch()
+        float *d_stats = nullptr, *d_snr = nullptr;
+        uint8_t *d_wid = nullptr;
+        int32_t *d_pts = nullptr;          // [1 + PB_SUBPOINT_WORDS * max]: count, then the points
+        float *d_best = nullptr;           // [tpitch] pb_search_subband_dm: best S/N
+        uint8_t *d_bestw = nullptr;        // [2][tpitch] its log2 width, its band
+        std::vector<hipEvent_t> ev;        // per pass: start, dedispersed, statistics; then kernels done, copy done
+        float ms[4] = {};                  // last pb_search_subbands: dedispersion, sums + statistics, boxcars + best, all with the copy
+    } sub;
 };
 
 // The dispersion delay of one channel in samples, in double: 4.148808e3 MHz^2 s (src/candidate.py:33) x DM x
@@ -197,12 +214,20 @@ SEARCH_LOCAL void search_refine_free(pb_search *s);
 SEARCH_LOCAL void search_giants_free(pb_search *s);
 SEARCH_LOCAL void search_gulp_free(pb_search *s);
 SEARCH_LOCAL void search_pol_free(pb_search *s);
+SEARCH_LOCAL void search_subbands_free(pb_search *s);
 
 // search_pol.hip, for search_run.hip: the transposition of a [nsamp][4][nchan] block into the four product planes and the
 // search plane d_xt (between ev[1] and ev[2]); codes: device bytes
 SEARCH_LOCAL int search_pol_transpose(pb_search *s, const uint8_t *codes, int nsamp);
 // search_cutout.hip, for search_pol.hip: k_cutout_ft over the requests in cut.d_req on a channel-major plane laid out as d_xt
 SEARCH_LOCAL void search_cutout_ft_launch(pb_search *s, const uint8_t *plane, int n, uint32_t *ft, uint32_t *fth);
+// search_cutout.hip, for search_subband.hip too: run = [nsub][2], each subband's run [first, last) of chans[] (zapped
+// channels are left out of chans[], so the unzapped channels of [b nchan/nsub, (b+1) nchan/nsub) are one run of it)
+SEARCH_LOCAL int search_sub_runs(pb_search *s, int nsub, std::vector<int32_t> &run);
+// search_run.hip, for search_subband.hip: k_prefix and k_series_stats, then k_boxcar (no peak list), on nrow series laid
+// out like d_D / d_P / d_stats / d_snr / d_wid, with the handle's baseline window and boxcars
+SEARCH_LOCAL void search_series_launch(pb_search *s, const uint32_t *D, uint64_t *P, float *stats, int nrow, int tout);
+SEARCH_LOCAL void search_boxcar_launch(pb_search *s, const uint64_t *P, const float *stats, float *snr, uint8_t *wid, int nrow, int tout);
 
 // search_run.hip, for search_stream.hip: the search from the cleaning on over the nsamp samples that d_xt holds (after
 // ev[2]; `cleaned`: leave the cleaning out, the block is cleaned already), and the copies to the host that end

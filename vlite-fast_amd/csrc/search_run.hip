@@ -19,7 +19,9 @@
 // The optional stages that act on what a run leaves on the device have a file each, kernels and host side together:
 // per-candidate cutouts (search_cutout.hip), a candidate's DM, width and S/N refined on a fine DM grid
 // (search_refine.hip), giants and clusters of giants (search_giants.hip), a candidate's Stokes spectra and rotation measure
-// (search_pol.hip, which also supplies the transposition of a four-product block).  The streaming stage (search_stream.hip)
+// (search_pol.hip, which also supplies the transposition of a four-product block), the sub-band search for band-limited
+// bursts (search_subband.hip, which runs k_prefix .. k_boxcar on its band series through search_series_launch and
+// search_boxcar_launch).  The streaming stage (search_stream.hip)
 // stands before the cleaning instead: it fills the channel-major block piece by piece and enters at search_block.  This file is the core -- create .. destroy,
 // run / peaks, the kernels of steps 1-3 -- and the cleaning, which launches k_dedisperse .. k_boxcar for its zero-DM
 // series.  The handle and the host helpers: search_internal.h; the device helpers: search_dev.h.
@@ -579,6 +581,7 @@ extern "C" void pb_search_destroy(pb_search *s)
     search_giants_free(s);
     search_gulp_free(s);
     search_pol_free(s);
+    search_subbands_free(s);
     search_release({s->d_codes, s->d_xt, s->d_delay, s->d_D, s->d_stats, s->d_snr, s->d_wid, s->d_P, s->d_peaks, s->d_chans},
                    nullptr, s->ev, 7);
     if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -655,6 +658,18 @@ static int search_clean(pb_search *s, int nsamp)
     }
     SCHK(s, hipEventRecord(s->rfi.ev[0], s->stream));
     return PB_OK;
+}
+
+void search_series_launch(pb_search *s, const uint32_t *D, uint64_t *P, float *stats, int nrow, int tout)
+{
+    k_prefix<<<nrow, 256, 0, s->stream>>>(D, P, tout, s->tpitch, s->ppitch());
+    k_series_stats<<<nrow, 256, 0, s->stream>>>(D, P, stats, tout, s->baseline, s->tpitch, s->ppitch());
+}
+
+void search_boxcar_launch(pb_search *s, const uint64_t *P, const float *stats, float *snr, uint8_t *wid, int nrow, int tout)
+{
+    k_boxcar<<<dim3((tout + 255) / 256, nrow), 256, 0, s->stream>>>(P, stats, snr, wid, tout, s->nbox, s->baseline, s->tpitch,
+                                                                    s->ppitch(), 0.f, nullptr, 0);
 }
 
 // From the channel-major block on: d_xt holds nsamp samples per channel and ev[2] has been recorded.  The cleaning (in

@@ -78,6 +78,7 @@ class Searcher(object):
         self._ref = None                 # (nstep, half_window, wmax, max_cands) once set_refine has switched it on
         self._gi = None                  # (sep_time, sep_dm, sep_filter, max_giants) once set_giants has switched it on
         self._pol = None                 # (off_len, guard, (rm_lo, rm_step, nrm), max_cands) once set_pol has switched it on
+        self._sub = None                 # (nsb, [(first, count), ..], max_points) once set_subbands has switched it on
         self.dms = dm_min + dm_step * np.arange(self.ndm) if dm_list is None else np.asarray(dm_list, np.float64)
         self._nsamp = 0
         self._tout = 0
@@ -324,6 +325,63 @@ class Searcher(object):
         t = (C.c_float * 2)()
         self._L.pb_search_refine_timers(self._s, t)
         return dict(kernels=float(t[0]), with_copy=float(t[1]))
+
+    def set_subbands(self, nsb=8, bands=None, dm_chunk=0, max_points=1 << 18):
+        """the sub-band search for band-limited bursts (include/pb_hip.h, pb_search_set_subbands): nsb base sub-bands (2, 4,
+        8 or 16), bands a list of (first, count) runs of them (None: subband_list(nsb)), the trial DMs processed dm_chunk at
+        a time (0: what keeps the stage within 1 GiB), up to max_points points per subbands() call; nsb=0 or an empty band
+        list switches the stage off"""
+        bands = subband_list(nsb) if (bands is None and nsb) else [(int(f), int(c)) for f, c in (bands or [])]
+        if not nsb:
+            bands = []
+        b2 = np.ascontiguousarray(np.asarray(bands, np.int32).reshape(-1, 2))
+        rc = self._L.pb_search_set_subbands(self._s, int(nsb), b2.ctypes.data_as(C.POINTER(C.c_int32)), len(bands),
+                                            int(dm_chunk), int(max_points))
+        self._check(rc, None, ValueError)
+        self._sub = (int(nsb), bands, int(max_points)) if bands else None
+
+    def subbands(self, thresh, t_lo=0, t_hi=None):
+        """pb_search_subbands on the block and planes of the last run() / peaks() / gulp search, samples [t_lo, t_hi) (t_hi
+        None: to the end): the cells where a band's S/N is >= thresh and above the full band's.  Returns dict(dmi, t, snr f32,
+        width_log2, band (index into the band list), snr_full f32 -- one entry per point, order unspecified --, npoints,
+        overflow); after an overflow (npoints > max_points) the arrays hold the first max_points points that arrived."""
+        if self._sub is None:
+            raise self._lp.PbError("the sub-band search is not switched on: call set_subbands() first")
+        if t_hi is None:
+            t_hi = self._tout
+        cap = self._sub[2]
+        buf = np.empty((cap, 6), np.int32)
+        n, ov = C.c_int(), C.c_int()
+        rc = self._L.pb_search_subbands(self._s, C.c_float(thresh), int(t_lo), int(t_hi), buf.ctypes.data_as(C.POINTER(C.c_int32)),
+                                        cap, C.byref(n), C.byref(ov))
+        self._check(rc, "pb_search_subbands")
+        b = buf[:min(n.value, cap)]
+        return dict(dmi=b[:, 0].copy(), t=b[:, 1].copy(), snr=b[:, 2].copy().view(np.float32), width_log2=b[:, 3].astype(np.uint8),
+                    band=b[:, 4].copy(), snr_full=b[:, 5].copy().view(np.float32), npoints=n.value, overflow=bool(ov.value))
+
+    def subband_dm(self, dmi):
+        """one trial DM of the current block through the sub-band kernels (tests, diagnostics): dict(sub [nsb][tout] u32,
+        band_snr f32, band_wid u8 [nbands][tout], band_stats [nbands][2], best_snr f32, best_wid, best_band u8 [tout])"""
+        if self._sub is None:
+            raise self._lp.PbError("the sub-band search is not switched on: call set_subbands() first")
+        nsb, nb, tout = self._sub[0], len(self._sub[1]), self._tout
+        out = dict(sub=np.zeros((nsb, tout), np.uint32), band_snr=np.zeros((nb, tout), np.float32),
+                   band_wid=np.zeros((nb, tout), np.uint8), band_stats=np.zeros((nb, 2), np.float32),
+                   best_snr=np.zeros(tout, np.float32), best_wid=np.zeros(tout, np.uint8), best_band=np.zeros(tout, np.uint8))
+        fp, u8p = C.POINTER(C.c_float), C.POINTER(C.c_uint8)
+        rc = self._L.pb_search_subband_dm(self._s, int(dmi), out["sub"].ctypes.data_as(C.POINTER(C.c_uint32)),
+                                          out["band_snr"].ctypes.data_as(fp), out["band_wid"].ctypes.data_as(u8p),
+                                          out["band_stats"].ctypes.data_as(fp), out["best_snr"].ctypes.data_as(fp),
+                                          out["best_wid"].ctypes.data_as(u8p), out["best_band"].ctypes.data_as(u8p))
+        self._check(rc, "pb_search_subband_dm")
+        return out
+
+    def subband_timers(self):
+        """device ms of the last subbands() call: the sub-band dedispersion; band sums, prefix sums and statistics; boxcars
+        and best band; everything with the copy to the host"""
+        t = (C.c_float * 4)()
+        self._L.pb_search_subband_timers(self._s, t)
+        return dict(zip(("dedisperse", "stats", "boxcar", "with_copy"), [float(v) for v in t]))
 
     def set_giants(self, sep_time=3, sep_dm=200, sep_filter=3, max_giants=1 << 18):
         """giants and clusters of giants on the device (include/pb_hip.h, pb_search_set_giants): hot samples of a series
@@ -629,6 +687,35 @@ def candidates_from_giants(res, dms, tsamp, sample0=0):
                  npoints=int(res["npoints"][k])) for k in order]
 
 
+def subband_list(nsb):
+    """the default band list of the sub-band search (include/pb_hip.h, pb_search_set_subbands, rule 2): runs (first, count)
+    of the nsb base sub-bands, staggered dyadic, widest first -- for c = nsb/2, nsb/4, .. 1 the bands (k max(c/2, 1), c),
+    k = 0, 1, .. while they fit: 2, 7, 18, 41 bands for nsb 2, 4, 8, 16"""
+    if nsb not in (2, 4, 8, 16):
+        raise ValueError("subband_list: nsb must be 2, 4, 8 or 16")
+    out, c = [], nsb // 2
+    while c >= 1:
+        step = max(c // 2, 1)
+        out += [(k * step, c) for k in range((nsb - c) // step + 1)]
+        c //= 2
+    return out
+
+
+def candidates_from_subbands(res, dms, tsamp, bands, nsb, fch1, foff, nchan, sample0=0):
+    """Searcher.subbands' points as candidates: one group_points call over all of them, whatever their band; each dict also
+    gets band = (first, count) and snr_full of the point at the candidate's (dmi, peak) -- there is one point per cell --
+    and f_lo, f_hi in MHz, the outer edges of the band's channels [first nchan/nsb, (first + count) nchan/nsb)."""
+    cands = group_points(res["dmi"], res["t"], res["snr"], 1 << np.asarray(res["width_log2"], np.int64), dms, tsamp, sample0=sample0)
+    at = {(int(d), int(t)): i for i, (d, t) in enumerate(zip(res["dmi"], res["t"]))}
+    per = nchan // nsb
+    for c in cands:
+        i = at[(c["dmi"], c["peak_idx"] - sample0)]
+        first, count = bands[int(res["band"][i])]
+        edges = [fch1 + (first * per - 0.5) * foff, fch1 + ((first + count) * per - 0.5) * foff]
+        c.update(band=(int(first), int(count)), f_lo=float(min(edges)), f_hi=float(max(edges)), snr_full=float(res["snr_full"][i]))
+    return cands
+
+
 def gulp_cuts(since, nsamp, gulp):
     """Where a piece of nsamp samples is cut when `since` samples (0 <= since < gulp) have accumulated since the last
     fire and a fire is due every `gulp` new samples: a list of (first sample of the part within the piece, its length,
@@ -685,11 +772,25 @@ class GulpSearch(object):
     are [nsamp][4 nchan] (AA, BB, CR, CI rows per sample) and the same selection gets a "pol" entry -- the candidate's slice
     of Searcher.pol for the request (dmi, peak in block coordinates, min(2^tfilt, 64)): on, non, off, noff, F, kbest, summary,
     rms, freqs; with cutouts also on the strongest of them, as many as the cutouts' max_cands, also carry pft, pft_hits and
-    tscr of Searcher.pol_cutouts.  feed() and feed_plane() raise."""
+    tscr of Searcher.pol_cutouts.  feed() and feed_plane() raise.
+    subbands=dict(thresh=..., send=False) (the searcher's set_subbands() must be on; not with pol=): every search is followed
+    by the sub-band search of the same block (Searcher.subbands, candidates_from_subbands) and push(), feed() and finish()
+    return the full-band candidates as before, followed by the sub-band candidates -- the ones that carry `band` -- of the
+    same samples.  Cutouts, refinement and the coincidencer see the full-band candidates only; with send=True the sub-band
+    candidates go to the coincidencer as well, as ordinary lines.  A gulp whose points exceed the searcher's max_points
+    yields no sub-band candidates and one log line."""
 
     def __init__(self, searcher, threshold=6.0, nbit=8, coincidencer=None, utc_start="1970-01-01-00:00:00", beam=1,
-                 cutouts=None, refine=None, giants=None, gulp=None, pol=None):
+                 cutouts=None, refine=None, giants=None, gulp=None, pol=None, subbands=None):
         self.s, self.threshold, self.nbit = searcher, threshold, nbit
+        self.sub = None
+        if subbands is not None:
+            if searcher._sub is None:
+                raise ValueError("GulpSearch(subbands=...): call the searcher's set_subbands() first")
+            if pol is not None:
+                raise ValueError("GulpSearch(subbands=...): not together with pol=")
+            self.sub = (float(subbands.get("thresh", threshold)), bool(subbands.get("send", False)))
+        self.pending_sub = None          # sub-band points of the latest gulp's last `ov` output samples (for finish())
         self.pol = None
         if pol is not None:
             if searcher._pol is None:
@@ -791,6 +892,31 @@ class GulpSearch(object):
             return []
         return candidates_from_giants(res, self.s.dms, self.s.tsamp, sample0=sample0)
 
+    def _sub_cands(self, res, sel, sample0):
+        """the sub-band candidates of the points `sel` of a subbands() result (None: the gulp was given up)"""
+        if res is None:
+            return []
+        s = self.s
+        sub = {k: res[k][sel] for k in ("dmi", "t", "snr", "width_log2", "band", "snr_full")}
+        return candidates_from_subbands(sub, s.dms, s.tsamp, s._sub[1], s._sub[0], s.fch1, s.foff, s.nchan, sample0=sample0)
+
+    def _sub_search(self, nout, tout, sample0):
+        """the sub-band search of the current block: the candidates of its samples [0, nout); the points of [nout, tout)
+        are kept for finish()"""
+        res = self.s.subbands(self.sub[0], 0, tout)
+        if res["overflow"]:
+            import sys
+            sys.stderr.write("search: sub-bands of the gulp at sample %d given up: %d points exceed max_points %d\n"
+                             % (sample0, res["npoints"], self.s._sub[2]))
+            res = None
+        self.pending_sub = (res, sample0, nout)
+        return self._sub_cands(res, res["t"] < nout, sample0) if res is not None else []
+
+    def _out(self, cands, sub, first, nsamps):
+        """send a batch (the sub-band candidates only with send=True) and return it, the sub-band candidates last"""
+        self._send(cands + sub if (sub and self.sub[1]) else cands, first, nsamps)
+        return cands + sub
+
     @staticmethod
     def _subset(pk, sel):
         return dict(dmi=pk["dmi"][sel], t=pk["t"][sel], snr=pk["snr"][sel], width_log2=pk["width_log2"][sel])
@@ -804,15 +930,14 @@ class GulpSearch(object):
         if data.shape[0] - self.s.max_delay < 64 + self.ov:
             self.tail = data                          # not enough yet for one output block
             return []
-        cands, first, nout = self._search_block(data, data.shape[0])
+        cands, sub, first, nout = self._search_block(data, data.shape[0])
         keep = min(self.s.max_delay + self.ov, data.shape[0])
         self.tail = data[data.shape[0] - keep:].copy()
-        self._send(cands, first, nout)
-        return cands
+        return self._out(cands, sub, first, nout)
 
     def _search_block(self, data, fill):
         """push()'s work from the search on: the block is `data` (host, [fill][nchan]) or, with data None, the `fill`
-        samples accumulated on the device.  Returns (candidates, first, nout)."""
+        samples accumulated on the device.  Returns (candidates, sub-band candidates, first, nout)."""
         if self.gi:
             # the same entry with a threshold no sample reaches: the block is searched, no point comes back
             pk = self.s.peaks(data, float("inf"), nbit=8, max_out=1) if data is not None else self.s.gulp_peaks(float("inf"), max_out=1)
@@ -829,8 +954,9 @@ class GulpSearch(object):
         self._cutouts(cands, first)
         self._refine(cands, first)
         self._pol(cands, first)
+        sub = self._sub_search(nout, pk["tout"], first) if self.sub else []
         self.done += nout
-        return cands, first, nout
+        return cands, sub, first, nout
 
     def _fire(self):
         """the accumulated block searched as push() searches tail + block, then its tail handed on"""
@@ -838,14 +964,14 @@ class GulpSearch(object):
         fill = self.fill
         if fill - self.s.max_delay < 64 + self.ov:
             return []                                 # not enough yet for one output block: nothing is dropped
-        cands, first, nout = self._search_block(None, fill)
+        cands, sub, first, nout = self._search_block(None, fill)
         # finish() cuts out and refines its candidates from the block of the latest search, which the advance below
         # and the pieces after it overwrite: where either is asked for, they are made now and kept for finish()
         self.early = self._pending_cands() if (self.cut or self.ref) else None
-        self._send(cands, first, nout)
+        out = self._out(cands, sub, first, nout)
         self.s.gulp_advance(min(self.s.max_delay + self.ov, fill))
         self.fill = min(self.s.max_delay + self.ov, fill)
-        return cands
+        return out
 
     def feed(self, codes=None, nbit=8, device_ptr=None, nsamp=None):
         """GulpSearch(gulp=N): a piece of the stream, any number of samples of nbit bits in SIGPROC order -- a host uint8
@@ -921,17 +1047,25 @@ class GulpSearch(object):
         self._pol(cands, sample0)
         return cands
 
+    def _pending_sub(self):
+        """the sub-band candidates of the same samples, from the points that the latest search kept (no device work)"""
+        if not self.sub or self.pending_sub is None:
+            return []
+        res, sample0, nout = self.pending_sub
+        self.pending_sub = None
+        return self._sub_cands(res, res["t"] >= nout, sample0) if res is not None else []
+
     def _finish(self):
         if self.pending is None:
             return []
         early = getattr(self, "early", None)
         cands = early if early is not None else self._pending_cands()
+        sub = self._pending_sub()
         _, sample0, tout = self.pending
         self.pending = None
         self.last_first = self.done
-        self._send(cands, self.done, tout - (self.done - sample0))
-        self.done = sample0 + tout
-        return cands
+        first, self.done = self.done, sample0 + tout
+        return self._out(cands, sub, first, tout - (first - sample0))
 
 
 def candidate_line(c):
@@ -947,7 +1081,9 @@ def arg_parser(with_file=True):
     ap = argparse.ArgumentParser(prog="search" if with_file else "--search", prefix_chars="-",
                                  epilog="with -f also: -pol [-pol_thresh S] [-pol_max N] [-rm LO HI] [-rm_step D] [-pol_off L G]: "
                                         "a nifs 4 filterbank (AA, BB, CR, CI); Stokes spectra and RM synthesis of the strongest "
-                                        "candidates (pol_parser)")
+                                        "candidates (pol_parser).  Also: -subbands N [-subband_thresh S] [-subband_send]: search N base "
+                                        "sub-bands (2, 4, 8 or 16) and their staggered dyadic runs for band-limited bursts "
+                                        "(subband_parser)")
     if with_file:
         ap.add_argument("-f", dest="fil", required=True)
     ap.add_argument("-dm", nargs=2, type=float, default=list(HEIMDALL_DM))
@@ -995,9 +1131,20 @@ def pol_parser():
     return ap
 
 
+def subband_parser():
+    """the flags of -subbands, parsed apart from arg_parser()'s like -pol's: a command line without them gives the namespace
+    it always gave"""
+    import argparse
+    ap = argparse.ArgumentParser(prog="search", prefix_chars="-", add_help=False, allow_abbrev=False)
+    ap.add_argument("-subbands", type=int, default=0, help="search N base sub-bands (2, 4, 8 or 16) and their staggered dyadic runs for band-limited bursts; 0: off; with -output_dir a .subband file beside each .cand")
+    ap.add_argument("-subband_thresh", type=float, default=None, help="with -subbands: lowest sub-band S/N reported (default: -detect_thresh)")
+    ap.add_argument("-subband_send", action="store_true", help="with -subbands: send the sub-band candidates to the coincidencer too")
+    return ap
+
+
 def parse_flags(flags):
     """process_baseband's --search "<flags>": the string split as a shell would and parsed by the search's own parser
-    (arg_parser(with_file=False) and parse_args' checks); an unknown flag, -f, -stream_chunk or -pol ends in SystemExit"""
+    (arg_parser(with_file=False) and parse_args' checks); an unknown flag, -f, -stream_chunk or -pol ends in SystemExit; -subbands and its two flags are taken"""
     import shlex
     return parse_args(shlex.split(flags), with_file=False)
 
@@ -1008,6 +1155,7 @@ def parse_args(argv=None, with_file=True):
     ap = arg_parser(with_file)
     argv = sys.argv[1:] if argv is None else list(argv)
     pa, rest = pol_parser().parse_known_args(argv)
+    sa, rest = subband_parser().parse_known_args(rest)
     a = ap.parse_args(rest)
     alone = [f for f in ("-pol_thresh", "-pol_max", "-rm", "-rm_step", "-pol_off") if f in argv]
     if alone and not pa.pol:
@@ -1028,6 +1176,17 @@ def parse_args(argv=None, with_file=True):
         ap.error("-cand_sep_dm and -cand_sep_filter must be >= 0")
     if not 1 <= a.max_giants <= 1 << 22:
         ap.error("-max_giants must be in 1..4194304")
+    if sa.subbands not in (0, 2, 4, 8, 16):
+        ap.error("-subbands must be 0, 2, 4, 8 or 16")
+    if (sa.subband_thresh is not None or sa.subband_send) and not sa.subbands:
+        ap.error("-subband_thresh, -subband_send: only with -subbands")
+    if sa.subbands:
+        if pa.pol:
+            ap.error("-subbands is not combined with -pol")
+        if sa.subband_thresh is None:
+            sa.subband_thresh = a.detect_thresh
+        for k, v in vars(sa).items():               # (only with -subbands: without it the namespace is what it always was)
+            setattr(a, k, v)
     if with_file and a.stream_chunk < 0:
         ap.error("-stream_chunk must be >= 0")
     if pa.pol:
@@ -1135,6 +1294,22 @@ def write_refined(path, cands):
     return len(cc)
 
 
+def subband_line(c):
+    """a sub-band candidate's line followed by its band (first base sub-band, how many), the band's edges in MHz and the
+    full-band S/N at its peak"""
+    return "%s\t%d\t%d\t%.4f\t%.4f\t%.4f" % (candidate_line(c), c["band"][0], c["band"][1], c["f_lo"], c["f_hi"], c["snr_full"])
+
+
+def write_subbands(path, cands):
+    """The sub-band candidates of one gulp (those that carry `band`), one subband_line each.  Returns how many were written
+    (0: no file)."""
+    cc = [c for c in cands if "band" in c]
+    if cc:
+        with open(path, "w") as f:
+            f.write("".join(subband_line(c) + "\n" for c in cc))
+    return len(cc)
+
+
 def gulp_stem(utc_start, first_sample, tsamp, beam):
     """<UTC of the gulp's first sample>_<beam, two digits>: the name heimdall gives a gulp's candidate file, as far as
     this project knows it (unpinned)"""
@@ -1183,31 +1358,44 @@ def open_search(a, hdr, gulp, device=None, searcher=None):
         s.set_pol(off_len=a.pol_off[0], guard=a.pol_off[1], rm=(a.rm[0], a.rm_step, rm_trials(a.rm[0], a.rm[1], a.rm_step)),
                   max_cands=a.pol_max)
         pol = dict(thresh=a.pol_thresh, max_per_gulp=a.pol_max)
+    sub = None
+    if getattr(a, "subbands", 0):
+        if nchan % a.subbands:
+            raise SystemExit("search -subbands: %d does not divide the %d channels" % (a.subbands, nchan))
+        s.set_subbands(nsb=a.subbands)
+        sub = dict(thresh=a.subband_thresh, send=a.subband_send)
     gi = dict(sep_time=a.cand_sep_time, sep_dm=a.cand_sep_dm, sep_filter=a.cand_sep_filter,
               max_giants=a.max_giants) if a.giants else None
     g = GulpSearch(s, threshold=a.detect_thresh, coincidencer=a.coincidencer, utc_start=utc, beam=a.beam, cutouts=cut,
-                   refine=ref, giants=gi, gulp=gulp, pol=pol)
+                   refine=ref, giants=gi, gulp=gulp, pol=pol, subbands=sub)
     if a.output_dir:
         os.makedirs(a.output_dir, exist_ok=True)
     stems = set()
 
-    def emit(cands):
+    def emit(batch):
+        cands = [c for c in batch if "band" not in c]
         for c in cands:
             print(candidate_line(c))
-        if a.output_dir and cands:
+        for c in batch:
+            if "band" in c:
+                print(subband_line(c))
+        if a.output_dir and batch:
             stem = gulp_stem(utc, g.last_first, tsamp, a.beam)
             if stem in stems:                       # gulps shorter than a second: keep the names apart
                 stem = "%s.%d_%02d" % (stem[:-3], g.last_first, a.beam)
             stems.add(stem)
-            with open(os.path.join(a.output_dir, stem + ".cand"), "w") as f:
-                f.write("".join(candidate_line(c) + "\n" for c in cands))
+            if cands:
+                with open(os.path.join(a.output_dir, stem + ".cand"), "w") as f:
+                    f.write("".join(candidate_line(c) + "\n" for c in cands))
+            if sub:
+                write_subbands(os.path.join(a.output_dir, stem + ".subband"), batch)
             if a.cutouts:
                 write_cutouts_npz(os.path.join(a.output_dir, stem + ".cutouts.npz"), cands, tsamp)
             if a.refine:
                 write_refined(os.path.join(a.output_dir, stem + ".refined"), cands)
             if pol:
                 write_pol(os.path.join(a.output_dir, stem + ".pol"), cands, tsamp)
-        return len(cands)
+        return len(batch)
 
     return s, g, emit
 
@@ -1226,6 +1414,10 @@ def main(argv=None):
     the strongest candidates of each gulp Stokes spectra and an RM synthesis (-rm, -rm_step, -pol_off; uncalibrated:
     include/pb_hip.h, pb_search_set_pol); with -output_dir a .pol file (each line followed by RM, L/I, V/I, position angle
     in degrees) and a .pol.npz beside each .cand.
+    -subbands N (2, 4, 8 or 16) follows each gulp's search with the sub-band search for band-limited bursts (include/pb_hip.h,
+    pb_search_set_subbands; -subband_thresh, default -detect_thresh): the sub-band candidates are printed after the gulp's
+    full-band lines, each as its nine columns followed by band_first band_count f_lo f_hi snr_full, and with -output_dir
+    written to a .subband file beside .cand, which stays as it is; -subband_send also sends them to the coincidencer.
     -stream_chunk M reads the file in pieces of M samples and feeds them to GulpSearch(gulp=-nsamps_gulp): the same
     lines, gathered on the GPU as a host behind pb_process would gather them; on this path 4- and 2-bit files are
     accepted and fed packed."""
