@@ -380,6 +380,61 @@ int pb_search_rfi_info(const pb_search *s, uint64_t *n_narrow, int *n_broad_samp
  * nbytes >= nchan * nsamp */
 int pb_search_fetch_clean(pb_search *s, uint8_t *xt, size_t nbytes);
 
+/* The cleaning's channel stage: channels that are noisy for the whole block.  A channel with persistent narrow-band
+ * interference has an inflated MAD, so the narrow pass finds no outlier in it, and the broad pass looks at time samples;
+ * such a channel enters every dedispersed sum at full weight.  This stage makes a per-block channel mask after IQRM
+ * (inter-quartile range mitigation, Morello et al. 2022): each channel's spread is compared with its neighbours' at a
+ * geometric sequence of lags, a channel whose spread is an outlier of the lagged differences is accused, and a vote
+ * count keeps one abnormally quiet channel from convicting its neighbours.  The definition below is THIS project's own,
+ * after IQRM; parity with any other implementation is not claimed.  Off until pb_search_set_rfi_chan; a pb_search on
+ * which it was never switched on allocates nothing more, launches nothing more and returns the bytes it returns without
+ * it.  Independent of pb_search_set_rfi: either, both or neither may be on.
+ * Notation as under pb_search_set_cutouts: xt[c][t] the channel-major u8 block of nsamp samples, chans[0 .. nact) the
+ * unzapped channels in ascending order.  The stage works on the compacted index a = 0 .. nact - 1, so a zapped range
+ * simply brings its two neighbours next to each other.  Everything is exact integer arithmetic except the one
+ * comparison marked binary64.
+ *   moments   of the block as handed to the search, before the narrow and broad passes, over t in [0, nsamp), 64-bit:
+ *             sum[a] = sum_t x, sq[a] = sum_t x^2, x = xt[chans[a]][t].
+ *             S[a] = nsamp sq[a] - sum[a]^2: nsamp^2 times the variance; nsamp is the same for every channel, so the
+ *             S[a] compare like variances without a division.
+ *             fill[a] = (2 sum[a] + nsamp) / (2 nsamp), integer division: the rounded mean.
+ *   lags      l = 1; while l <= radius: take +l, then -l; l = max(l * 3 / 2, l + 1), integer division.  radius = 0
+ *             means max(1, nact / 10).
+ *   outliers  of one signed lag L: j(a) = min(max(a - L, 0), nact - 1); d[a] = S[a] - S[j(a)], int64.  With the nact
+ *             values of d sorted ascending: q1 = d_sorted[(nact - 1) / 4], med = d_sorted[(nact - 1) / 2],
+ *             q3 = d_sorted[3 (nact - 1) / 4], integer division, no interpolation (only values are used, so ties are
+ *             harmless).  Channel a is an outlier of lag L iff
+ *                 (double)(d[a] - med) > (double)tol * ((double)(q3 - q1) / 1.349)
+ *             -- the differences in int64 first, then one conversion each, one quotient and one product in binary64,
+ *             none contracted; tol is the binary32 argument widened.  One-sided: high spread only.
+ *   votes     for every (L, a) with a an outlier of L: recv[a] += 1 and cast[j(a)] += 1.  Integer counts over all lags,
+ *             independent of any order.
+ *   mask      flag[a] = 1 iff there is at least one such (L, a) with cast[j(a)] <= recv[a]: the accuser must not have
+ *             accused more channels than the accused has accusers.  One pass, no iteration.
+ *   fill      every flagged channel becomes xt[chans[a]][t] = fill[a] for t in [0, nsamp), in place, before the narrow
+ *             and broad passes, which then run, if switched on, exactly as they do on any block (a constant channel has
+ *             MAD 0 and no outlier).  Zapped channels and samples at or beyond nsamp are not touched.
+ * Consequences.  Everything after the cleaning reads the filled block, as with the existing cleaning: dedispersion,
+ * statistics, boxcars, giants, cutouts, refinement, the sub-band search, pb_search_fetch_clean.  With polarisation on
+ * the stage changes xt only; the four product planes stay what the file held.  nact and the delay table are unchanged:
+ * a flagged channel contributes a constant to every series.
+ * Streaming.  A gulp call cleans the accumulated block in place once, under the rules of pb_search_gulp_peaks: the raw
+ * tail is put aside first and handed on raw, a second call on the same block keeps the first call's mask, and the next
+ * gulp makes its own mask from its own block.
+ * pb_search_set_rfi_chan(s, radius, tol): tol > 0 switches the stage on (search.py's default: radius 0, tol 4), tol == 0
+ * switches it off and frees its buffers.  PB_EINVAL with nothing changed for radius < 0 or radius > nact, for a tol that
+ * is negative or not finite, and for a handle beyond what the kernels are built for: max_samples > 8 388 608 (a lane's
+ * 32-bit partial sums of x^2, and 255^2 nsamp^2 < 2^63 for S) or nact > 8192 (the sort's 64 KiB of LDS).
+ * tests/search_rfichan_ref.py restates the definition; tests/test_gpu_search_rfichan.py holds the kernels to it exactly. */
+int pb_search_set_rfi_chan(pb_search *s, int radius, float tol);
+/* the last block's channel stage (host, any pointer may be NULL): *nflag = flagged channels; mask u8 [nchan], sum and
+ * stat (= S) i64 [nchan], recv and cast i32 [nchan], fill u8 [nchan], all in file channel numbering and 0 for zapped
+ * channels; *ms = device time of the stage, from events of its own.  Everything is 0 when the last block did not go
+ * through the stage.  pb_search_timers keeps its meaning (the stage lies inside the cleaning window that its third
+ * entry excludes), and so does pb_search_rfi_info: its ms is the narrow and broad passes'. */
+int pb_search_rfi_chan_info(pb_search *s, int *nflag, uint8_t *mask, int64_t *sum, int64_t *stat, int32_t *recv,
+                            int32_t *cast, uint8_t *fill, float *ms);
+
 /* Per-candidate cutouts of the LAST block given to pb_search_run / pb_search_peaks, taken from what is still on the
  * device: the dedispersed frequency-time image of an event and its DM-time "bow tie".  heimdall writes no such images:
  * the definition is THIS project's own, every value an exact integer.  Off until pb_search_set_cutouts; a pb_search on

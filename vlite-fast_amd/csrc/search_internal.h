@@ -1,5 +1,5 @@
 // What the search's translation units share on the host side: the handle, the dispersion delay, the error and timer
-// helpers, and each stage's free function.  search_run.hip holds the core (create .. fetch_clean) and the RFI cleaning;
+// helpers, and each stage's free function.  search_run.hip holds the core (create .. fetch_clean) and the RFI cleaning, search_rfichan.hip the cleaning's channel stage;
 // search_cutout.hip, search_refine.hip, search_giants.hip, search_stream.hip, search_pol.hip and search_subband.hip one optional stage each, kernels and host side together (a
 // kernel lives in the file that launches it); search_plane.hip the streaming stage's entry for fp32 planes.  Device-only helpers: search_dev.h.
 #pragma once
@@ -62,6 +62,20 @@ struct pb_search {
         int n_broad = 0;
         float ms = 0.f;
     } rfi;
+    // the cleaning's channel stage (pb_search_set_rfi_chan); the buffers exist while it is switched on (tol > 0)
+    struct {
+        int radius = 0, nlag = 0, npad = 0;
+        float tol = 0.f;
+        int ran = 0;                       // whether the last block went through the stage
+        int have = 0;                      // the buffers hold the results of the block in d_xt (a gulp cleaned in place keeps them)
+        int launched = 0;                  // the last search_block launched the stage itself
+        int32_t *d_lags = nullptr;         // [nlag] signed lags
+        int64_t *d_mom = nullptr;          // [2][nact] sum, S of each unzapped channel
+        uint8_t *d_fill = nullptr, *d_mask = nullptr;  // [nact] rounded mean; flag
+        uint8_t *d_tab = nullptr;          // [nlag][nact] outlier of the lag
+        int32_t *d_cnt = nullptr;          // [2][nact] recv, cast; then nflag
+        hipEvent_t ev[3] = {};             // start, end of the stage; end of the cleaning window where narrow and broad are off
+    } chan;
     // cutouts (pb_search_set_cutouts); the buffers exist while it is switched on (max > 0)
     struct {
         int nsub = 0, nt = 0, ndmrow = 0, max = 0;
@@ -209,6 +223,7 @@ static inline void search_release(std::initializer_list<void *> dev, void *host,
 }
 
 SEARCH_LOCAL void search_rfi_free(pb_search *s);
+SEARCH_LOCAL void search_rfichan_free(pb_search *s);
 SEARCH_LOCAL void search_cutouts_free(pb_search *s);
 SEARCH_LOCAL void search_refine_free(pb_search *s);
 SEARCH_LOCAL void search_giants_free(pb_search *s);
@@ -216,6 +231,8 @@ SEARCH_LOCAL void search_gulp_free(pb_search *s);
 SEARCH_LOCAL void search_pol_free(pb_search *s);
 SEARCH_LOCAL void search_subbands_free(pb_search *s);
 
+// search_rfichan.hip, for search_run.hip: the channel stage on the nsamp samples of d_xt, in place
+SEARCH_LOCAL int search_rfichan_launch(pb_search *s, int nsamp);
 // search_pol.hip, for search_run.hip: the transposition of a [nsamp][4][nchan] block into the four product planes and the
 // search plane d_xt (between ev[1] and ev[2]); codes: device bytes
 SEARCH_LOCAL int search_pol_transpose(pb_search *s, const uint8_t *codes, int nsamp);

@@ -576,6 +576,7 @@ extern "C" void pb_search_destroy(pb_search *s)
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     search_rfi_free(s);
+    search_rfichan_free(s);
     search_cutouts_free(s);
     search_refine_free(s);
     search_giants_free(s);
@@ -680,6 +681,14 @@ int search_block(pb_search *s, int nsamp, float thresh, bool want_peaks, bool cl
 {
     const int tout = nsamp - s->max_delay;
     s->rfi.ran = s->rfi.narrow || s->rfi.broad;
+    // the channel stage (search_rfichan.hip) comes first; a block cleaned already keeps the results of its first search
+    s->chan.launched = s->chan.tol > 0 && !cleaned;
+    s->chan.ran = s->chan.launched || (s->chan.tol > 0 && s->chan.have);
+    if (s->chan.launched) {
+        const int rc = search_rfichan_launch(s, nsamp);
+        if (rc) return rc;
+    }
+    if (s->chan.tol > 0 && !s->rfi.ran) SCHK(s, hipEventRecord(s->chan.ev[2], s->stream));
     if (s->rfi.ran && cleaned) {
         SCHK(s, hipEventRecord(s->rfi.ev[0], s->stream));
     } else if (s->rfi.ran) {
@@ -743,7 +752,9 @@ static int search_run(pb_search *s, const void *codes, int codes_on_device, int 
 // the cleaning ends)
 static int search_times(pb_search *s)
 {
-    for (int i = 0; i < 6; ++i) s->ms[i] = search_ms((i == 2 && s->rfi.ran) ? s->rfi.ev[0] : s->ev[i], s->ev[i + 1]);
+    // the dedispersion starts where the cleaning window ends: after narrow / broad, else after the channel stage
+    hipEvent_t dd = s->rfi.ran ? s->rfi.ev[0] : (s->chan.tol > 0 ? s->chan.ev[2] : s->ev[2]);
+    for (int i = 0; i < 6; ++i) s->ms[i] = search_ms(i == 2 ? dd : s->ev[i], s->ev[i + 1]);
     s->rfi.n_narrow = 0;
     s->rfi.n_broad = 0;
     s->rfi.ms = 0.f;
@@ -752,7 +763,7 @@ static int search_times(pb_search *s)
         SCHK(s, hipMemcpy(c, s->rfi.d_rcnt, sizeof c, hipMemcpyDeviceToHost));
         s->rfi.n_narrow = c[0];
         s->rfi.n_broad = (int)c[1];
-        s->rfi.ms = search_ms(s->ev[2], s->rfi.ev[0]);
+        s->rfi.ms = search_ms(s->chan.launched ? s->chan.ev[1] : s->ev[2], s->rfi.ev[0]);
     }
     return PB_OK;
 }

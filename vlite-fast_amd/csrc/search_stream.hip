@@ -193,7 +193,7 @@ static int gulp_search(pb_search *s, const char *fn, float thresh, bool want_pea
     SCHK(s, hipSetDevice(s->device));
     SCHK(s, hipEventRecord(s->ev[0], s->stream));
     SCHK(s, hipEventRecord(s->ev[1], s->stream));
-    const bool clean = s->rfi.narrow || s->rfi.broad;
+    const bool clean = s->rfi.narrow || s->rfi.broad || s->chan.tol > 0;
     if (clean && !s->gp.cleaned) {
         rc = gulp_save(s, fill - std::min(s->gp.keep_max, fill), std::min(s->gp.keep_max, fill));
         if (rc) return rc;

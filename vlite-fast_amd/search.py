@@ -72,6 +72,11 @@ class Searcher(object):
         self._L.pb_search_info(self._s, C.byref(ndm), C.byref(nbox), C.byref(md))
         self.ndm, self.nbox, self.max_delay = ndm.value, nbox.value, md.value
         self.nchan, self.tsamp = nchan, tsamp
+        zapped = np.zeros(nchan, bool)
+        for lo, hi in zap:
+            zapped[max(lo, 0):max(hi, 0)] = True
+        self.chans = np.nonzero(~zapped)[0]     # the unzapped channels, ascending
+        self.nact = int(self.chans.size)
         self.max_samples = max_samples
         self.fch1, self.foff = fch1, foff
         self._cut = None                 # (nsub, nt, ndmrow, max_cands) once set_cutouts has switched them on
@@ -79,6 +84,7 @@ class Searcher(object):
         self._gi = None                  # (sep_time, sep_dm, sep_filter, max_giants) once set_giants has switched it on
         self._pol = None                 # (off_len, guard, (rm_lo, rm_step, nrm), max_cands) once set_pol has switched it on
         self._sub = None                 # (nsb, [(first, count), ..], max_points) once set_subbands has switched it on
+        self._rfichan = None             # (radius, tol) once set_rfi_chan has switched the channel stage on
         self.dms = dm_min + dm_step * np.arange(self.ndm) if dm_list is None else np.asarray(dm_list, np.float64)
         self._nsamp = 0
         self._tout = 0
@@ -123,6 +129,28 @@ class Searcher(object):
         n, b, ms = C.c_uint64(), C.c_int(), C.c_float()
         self._L.pb_search_rfi_info(self._s, C.byref(n), C.byref(b), C.byref(ms))
         return dict(n_narrow=int(n.value), n_broad_samples=int(b.value), ms=float(ms.value))
+
+    def set_rfi_chan(self, radius=0, tol=4.0):
+        """the cleaning's channel stage (include/pb_hip.h, pb_search_set_rfi_chan): of every following block the channels
+        whose spread is an outlier among their neighbours' (lags up to radius; 0: a tenth of the unzapped channels) are
+        filled with their rounded mean before the narrow and broad passes; tol=0 switches it off"""
+        rc = self._L.pb_search_set_rfi_chan(self._s, int(radius), float(tol))
+        self._check(rc, None, ValueError)
+        self._rfichan = (int(radius), float(tol)) if tol > 0 else None
+
+    def rfi_chan_info(self):
+        """the last block's channel stage: dict(nflag, mask u8, sum, stat i64, recv, cast i32, fill u8 -- [nchan], file
+        channel numbering, 0 for zapped channels --, ms); all zero when the block did not go through the stage"""
+        n, ms = C.c_int(), C.c_float()
+        out = dict(mask=np.zeros(self.nchan, np.uint8), sum=np.zeros(self.nchan, np.int64), stat=np.zeros(self.nchan, np.int64),
+                   recv=np.zeros(self.nchan, np.int32), cast=np.zeros(self.nchan, np.int32), fill=np.zeros(self.nchan, np.uint8))
+        i64p, i32p, u8p = C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+        rc = self._L.pb_search_rfi_chan_info(self._s, C.byref(n), out["mask"].ctypes.data_as(u8p), out["sum"].ctypes.data_as(i64p),
+                                             out["stat"].ctypes.data_as(i64p), out["recv"].ctypes.data_as(i32p),
+                                             out["cast"].ctypes.data_as(i32p), out["fill"].ctypes.data_as(u8p), C.byref(ms))
+        self._check(rc, "pb_search_rfi_chan_info")
+        out.update(nflag=int(n.value), ms=float(ms.value))
+        return out
 
     def fetch_clean(self):
         """the last run's channel-major block [nchan][nsamp] u8 as dedispersion read it (cleaned if cleaning was on)"""
@@ -747,7 +775,8 @@ class GulpSearch(object):
     became complete; finish() those of the stream's last widest - 1 samples (narrow widths only: there is no more
     data); sample indices count from the start of the stream.  With RFI cleaning on (Searcher.set_rfi) every block is
     cleaned with its own statistics, as heimdall cleans per gulp: the carried-over tail is cleaned again inside the
-    next block.
+    next block.  With the channel stage on (Searcher.set_rfi_chan) every block also gets its own channel mask, and
+    chan_log holds (first sample, Searcher.rfi_chan_info()) of each block that the latest push() / feed() / finish() searched.
     cutouts=dict(thresh=..., max_per_gulp=...) (the searcher's set_cutouts() must be on): of each push()'s or
     finish()'s candidates those at or above thresh, strongest first, at most max_per_gulp (and at most the searcher's
     max_cands), get a "cutout" entry -- dict(ft, ft_hits, dt, dt_hits, dm_rows, sub_freqs, tscr) of Searcher.cutouts
@@ -790,6 +819,7 @@ class GulpSearch(object):
             if pol is not None:
                 raise ValueError("GulpSearch(subbands=...): not together with pol=")
             self.sub = (float(subbands.get("thresh", threshold)), bool(subbands.get("send", False)))
+        self.chan_log = []               # (first sample, rfi_chan_info()) per block that the latest call searched (channel stage on)
         self.pending_sub = None          # sub-band points of the latest gulp's last `ov` output samples (for finish())
         self.pol = None
         if pol is not None:
@@ -926,6 +956,7 @@ class GulpSearch(object):
         if self.nbit != 8:
             raise ValueError("GulpSearch takes unpacked 8-bit samples")
         block = np.asarray(block, np.uint8).reshape(-1, self.nif * self.s.nchan)
+        self.chan_log = []
         data = np.concatenate([self.tail, block]) if self.tail.size else block
         if data.shape[0] - self.s.max_delay < 64 + self.ov:
             self.tail = data                          # not enough yet for one output block
@@ -951,6 +982,8 @@ class GulpSearch(object):
             cands = candidates_from_peaks(self._subset(pk, full), self.s.dms, self.s.tsamp, sample0=self.done)
             self.pending = (self._subset(pk, ~full), self.done, pk["tout"])
         first = self.last_first = self.done
+        if self.s._rfichan is not None:
+            self.chan_log.append((first, self.s.rfi_chan_info()))
         self._cutouts(cands, first)
         self._refine(cands, first)
         self._pol(cands, first)
@@ -1016,7 +1049,7 @@ class GulpSearch(object):
     def _feed(self, nsamp, push):
         """a piece of nsamp samples cut where the gulps end: push(first sample, length) appends a part and returns the
         block's new length; a fire follows each part that completes a gulp"""
-        out = []
+        out, self.chan_log = [], []
         for off, n, fire in gulp_cuts(self.since, nsamp, self.gulp):
             self.fill = push(off, n)
             self.since += n
@@ -1032,6 +1065,7 @@ class GulpSearch(object):
     def flush(self):
         """GulpSearch(gulp=N): search the partial gulp fed since the last fire now (finish() does it first; a caller that
         wants the two batches apart, each with its own last_first, calls flush() and then finish())"""
+        self.chan_log = []
         return self._fire() if self.gulp is not None and self.since > 0 else []
 
     def _pending_cands(self):
@@ -1142,9 +1176,21 @@ def subband_parser():
     return ap
 
 
+def rfichan_parser():
+    """the flags of -rfi_chan, parsed apart from arg_parser()'s like -pol's: a command line without them gives the namespace
+    it always gave"""
+    import argparse
+    ap = argparse.ArgumentParser(prog="search", prefix_chars="-", add_help=False, allow_abbrev=False)
+    ap.add_argument("-rfi_chan", action="store_true", help="flag the channels that are noisy for a whole gulp and fill them with their mean before the rest of the cleaning; with -output_dir a .chans file beside each .cand")
+    ap.add_argument("-rfi_chan_tol", type=float, default=None, help="with -rfi_chan: the outlier threshold in robust sigmas (default 4)")
+    ap.add_argument("-rfi_chan_radius", type=int, default=None, help="with -rfi_chan: the largest lag in unzapped channels (default 0: a tenth of them)")
+    return ap
+
+
 def parse_flags(flags):
     """process_baseband's --search "<flags>": the string split as a shell would and parsed by the search's own parser
-    (arg_parser(with_file=False) and parse_args' checks); an unknown flag, -f, -stream_chunk or -pol ends in SystemExit; -subbands and its two flags are taken"""
+    (arg_parser(with_file=False) and parse_args' checks); an unknown flag, -f, -stream_chunk or -pol ends in SystemExit; -subbands
+    and -rfi_chan and their flags are taken"""
     import shlex
     return parse_args(shlex.split(flags), with_file=False)
 
@@ -1156,6 +1202,7 @@ def parse_args(argv=None, with_file=True):
     argv = sys.argv[1:] if argv is None else list(argv)
     pa, rest = pol_parser().parse_known_args(argv)
     sa, rest = subband_parser().parse_known_args(rest)
+    ca, rest = rfichan_parser().parse_known_args(rest)
     a = ap.parse_args(rest)
     alone = [f for f in ("-pol_thresh", "-pol_max", "-rm", "-rm_step", "-pol_off") if f in argv]
     if alone and not pa.pol:
@@ -1176,6 +1223,17 @@ def parse_args(argv=None, with_file=True):
         ap.error("-cand_sep_dm and -cand_sep_filter must be >= 0")
     if not 1 <= a.max_giants <= 1 << 22:
         ap.error("-max_giants must be in 1..4194304")
+    if (ca.rfi_chan_tol is not None or ca.rfi_chan_radius is not None) and not ca.rfi_chan:
+        ap.error("-rfi_chan_tol, -rfi_chan_radius: only with -rfi_chan")
+    if ca.rfi_chan:
+        if ca.rfi_chan_tol is None:
+            ca.rfi_chan_tol = 4.0
+        if ca.rfi_chan_radius is None:
+            ca.rfi_chan_radius = 0
+        if not (ca.rfi_chan_tol > 0 and np.isfinite(ca.rfi_chan_tol)) or ca.rfi_chan_radius < 0:
+            ap.error("-rfi_chan_tol must be > 0 and finite, -rfi_chan_radius >= 0")
+        for k, v in vars(ca).items():               # (only with -rfi_chan: without it the namespace is what it always was)
+            setattr(a, k, v)
     if sa.subbands not in (0, 2, 4, 8, 16):
         ap.error("-subbands must be 0, 2, 4, 8 or 16")
     if (sa.subband_thresh is not None or sa.subband_send) and not sa.subbands:
@@ -1310,6 +1368,16 @@ def write_subbands(path, cands):
     return len(cc)
 
 
+def write_chans(path, info, s):
+    """One gulp's channel mask (Searcher.rfi_chan_info): the line `# nflag nact radius tol`, then `channel S fill recv` for
+    every flagged channel, ascending.  Written for every gulp searched with the channel stage on, flagged channels or not."""
+    radius, tol = s._rfichan
+    with open(path, "w") as f:
+        f.write("# %d %d %d %g\n" % (info["nflag"], s.nact, radius, tol))
+        for c in np.nonzero(info["mask"])[0]:
+            f.write("%d %d %d %d\n" % (c, info["stat"][c], info["fill"][c], info["recv"][c]))
+
+
 def gulp_stem(utc_start, first_sample, tsamp, beam):
     """<UTC of the gulp's first sample>_<beam, two digits>: the name heimdall gives a gulp's candidate file, as far as
     this project knows it (unpinned)"""
@@ -1341,6 +1409,8 @@ def open_search(a, hdr, gulp, device=None, searcher=None):
         s.set_baseline(int(a.baseline_length / tsamp))
         if a.rfi_clean:
             s.set_rfi(narrow=not a.rfi_no_narrow, broad=not a.rfi_no_broad, tol=a.rfi_tol)
+        if getattr(a, "rfi_chan", False):
+            s.set_rfi_chan(radius=a.rfi_chan_radius, tol=a.rfi_chan_tol)
     utc = _time.strftime("%Y-%m-%d-%H:%M:%S", _time.gmtime(round((hdr.get("tstart", 40587.0) - 40587.0) * 86400.0)))
     cut = None
     if a.cutouts:
@@ -1372,6 +1442,13 @@ def open_search(a, hdr, gulp, device=None, searcher=None):
         os.makedirs(a.output_dir, exist_ok=True)
     stems = set()
 
+    def new_stem(first):
+        stem = gulp_stem(utc, first, tsamp, a.beam)
+        if stem in stems:                           # gulps shorter than a second: keep the names apart
+            stem = "%s.%d_%02d" % (stem[:-3], first, a.beam)
+        stems.add(stem)
+        return stem
+
     def emit(batch):
         cands = [c for c in batch if "band" not in c]
         for c in cands:
@@ -1379,11 +1456,12 @@ def open_search(a, hdr, gulp, device=None, searcher=None):
         for c in batch:
             if "band" in c:
                 print(subband_line(c))
-        if a.output_dir and batch:
-            stem = gulp_stem(utc, g.last_first, tsamp, a.beam)
-            if stem in stems:                       # gulps shorter than a second: keep the names apart
-                stem = "%s.%d_%02d" % (stem[:-3], g.last_first, a.beam)
-            stems.add(stem)
+        stem = new_stem(g.last_first) if a.output_dir and batch else None
+        if a.output_dir:                            # the channel masks of the gulps that the call searched
+            for first, info in g.chan_log:                # (beside the batch's .cand where the gulp is the batch's)
+                cstem = stem if stem and first == g.last_first else new_stem(first)
+                write_chans(os.path.join(a.output_dir, cstem + ".chans"), info, s)
+        if stem:
             if cands:
                 with open(os.path.join(a.output_dir, stem + ".cand"), "w") as f:
                     f.write("".join(candidate_line(c) + "\n" for c in cands))
