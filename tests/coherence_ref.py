@@ -43,9 +43,10 @@ class CohState(object):
         self.bp = {0: np.zeros((2, NCHANOUT), F), 1: np.zeros((2, NCHANOUT), F)}
 
 
-def detect(X, w, bp, kur):
+def detect(X, w, bp, kur, clip_out=None):
     """One segment of one stream.  X [2][R][4096] complex64, w [2][R]; bp [2][4096] updated in place.
-    -> fp32 planes [4][R/8][4096] (AA, BB, CR, CI)"""
+    -> fp32 planes [4][R/8][4096] (AA, BB, CR, CI).  clip_out: a list that receives the segment's [2][R][4096] bool
+    array of samples that took the 11x clip (all False on the raw stream)"""
     R = X.shape[1]
     xr, xi = X.real.astype(F), X.imag.astype(F)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
@@ -104,6 +105,8 @@ def detect(X, w, bp, kur):
             zero = (w[0] == 0)[:, None] | (w[1] == 0)[:, None] | clip[0] | clip[1]
             cr = np.where(zero, F(0), cr)
             ci = np.where(zero, F(0), ci)
+    if clip_out is not None:
+        clip_out.append(clip)
     prod = [v[0], v[1], cr, ci]
     nt = R // NSCRUNCH
     out = np.zeros((4, nt, NCHANOUT), F)
@@ -150,18 +153,28 @@ def quantise(O, planes, nbit):
     return out
 
 
-def run(O, data, R, rfi_mode, nbit, delays=None, inject_now=0):
-    """data [nseg][2][R*12500] u8 -> {stream: (codes [nseg*trim], planes [nseg][4][R/8][4096])}"""
-    st = CohState()
+class Streams(dict):
+    """run's result: {stream: (codes, planes)}; .state is the CohState the run used and left updated"""
+    state = None
+
+
+def run(O, data, R, rfi_mode, nbit, delays=None, inject_now=0, state=None, clip_out=None):
+    """data [nseg][2][R*12500] u8 -> {stream: (codes [nseg*trim], planes [nseg][4][R/8][4096])}, a Streams.
+    state: the CohState to continue from (default: a fresh one); it is updated in place and returned as the result's
+    .state.  clip_out: a dict that receives {stream: [per segment the clip array of detect]}"""
+    st = CohState() if state is None else state
     codes = {0: [], 1: []}
     planes = {0: [], 1: []}
     inj = inject_now
     for s in range(data.shape[0]):
         since = (inj - 1) * R if (delays is not None and inj > 0) else None
         for stream, (X, w) in spectra(O, data[s], R, rfi_mode, delays, since).items():
-            p = detect(X, w, st.bp[stream], kur=stream == 1)
+            cl = None if clip_out is None else clip_out.setdefault(stream, [])
+            p = detect(X, w, st.bp[stream], kur=stream == 1, clip_out=cl)
             planes[stream].append(p)
             codes[stream].append(quantise(O, p, nbit))
         if inj > 0:
             inj += 1
-    return {k: (np.concatenate(codes[k]), np.stack(planes[k])) for k in codes if codes[k]}
+    out = Streams((k, (np.concatenate(codes[k]), np.stack(planes[k]))) for k in codes if codes[k])
+    out.state = st
+    return out

@@ -352,7 +352,8 @@ def test_gulps_carry_the_polarisation_of_their_candidates():
 
 
 def test_cli_writes_pol_files(tmp_path, capsys):
-    """search -pol on a nifs 4 file written here (not the filterbank host's: that seam is not covered): the candidate
+    """search -pol on a nifs 4 file written here (not the filterbank host's: that seam is covered by
+    test_the_self_test_pulse_of_a_coherence_file_goes_through_search_pol below): the candidate
     lines are those of the same file's total intensity searched without -pol, every gulp with polarised candidates gets a
     .pol file whose lines parse and a .pol.npz whose `on` sums equal the restatement applied to the file's bytes."""
     import os
