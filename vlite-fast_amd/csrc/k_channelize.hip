@@ -360,15 +360,16 @@ hipError_t launch_channelize(pb_handle *h, int nseg, int inject_now)
     }
     if (!consts_ok) return hipErrorInvalidValue;
     if (nseg <= 0) return hipSuccess;
+    const pb_handle::BufSet &b = h->set();
     ChanArgs a;
-    a.in = h->d_in;
+    a.in = b.d_in;
     a.in_ant_stride = (size_t)h->S * 2 * h->seg_samples;
     a.seg_samples = h->seg_samples;
-    a.wrow = h->d_wrow;
+    a.wrow = b.d_wrow;
     a.rowmask = pb_rowmask(h);
     a.wrow_ant_stride = (size_t)h->S * h->R;
-    a.Praw = h->d_Praw;
-    a.Pkur = h->d_Pkur;
+    a.Praw = b.d_Praw;
+    a.Pkur = b.d_Pkur;
     a.p_ant_stride = (size_t)h->S * 2 * h->R * PB_NCHANOUT;
     a.tw2 = h->ft.tw2;
     a.tw3 = h->ft.tw3;
@@ -386,9 +387,9 @@ hipError_t launch_channelize(pb_handle *h, int nseg, int inject_now)
     a.R = h->R;
     a.rfi_mode = h->cfg.rfi_mode;
     a.inject_now = inject_now;
-    a.flags = h->d_flags;
+    a.flags = b.d_flags;
     a.flags_ant_stride = (size_t)h->S * h->nblk_seg;
-    a.wrow_out = h->d_wrow;
+    a.wrow_out = b.d_wrow;
     a.rowmask_out = pb_rowmask(h);
     a.dag = h->d_dag;
     if (pb_fused_kurtosis(h)) {

@@ -367,27 +367,29 @@ hipError_t launch_pfb_weights(pb_handle *h, int nseg)
     const int nrows = nseg * h->R;
     dim3 g((nrows + 255) / 256, h->A);
     k_pfb_weights<<<g, 256, 0, h->stream>>>(pb_rowmask(h), (size_t)h->S * h->R,
-                                            h->d_hist_flags + (size_t)h->hist_rd * h->A * 3 * PB_BLK_PER_FFT, h->d_tapE, h->d_wrow, nrows);
+                                            h->d_hist_flags + (size_t)h->hist_rd * h->A * 3 * PB_BLK_PER_FFT, h->d_tapE,
+                                            h->set().d_wrow, nrows);
     return hipGetLastError();
 }
 
 hipError_t launch_channelize_pfb(pb_handle *h, int nseg, int inject_now)
 {
+    const pb_handle::BufSet &b = h->set();
     PfbArgs a;
-    a.in = h->d_in;
+    a.in = b.d_in;
     a.in_ant_stride = (size_t)h->S * 2 * h->seg_samples;
     a.seg_samples = h->seg_samples;
     a.hist = h->d_hist_in + (size_t)h->hist_rd * h->A * 2 * 3 * PFB_HIST_STRIDE;      // the slot this batch reads
-    a.flags = h->d_flags;
+    a.flags = b.d_flags;
     a.flags_ant_stride = (size_t)h->S * h->nblk_seg;
     a.hflags = h->d_hist_flags + (size_t)h->hist_rd * h->A * 3 * PB_BLK_PER_FFT;
     a.hvalid = h->d_hist_valid + (size_t)h->hist_rd * h->A * 3;
-    a.wrow = h->d_wrow;
+    a.wrow = b.d_wrow;
     a.rowmask = pb_rowmask(h);
     a.wrow_ant_stride = (size_t)h->S * h->R;
     a.fir = h->ft.taps_n;
-    a.Praw = h->d_Praw;
-    a.Pkur = h->d_Pkur;
+    a.Praw = b.d_Praw;
+    a.Pkur = b.d_Pkur;
     a.p_ant_stride = (size_t)h->S * 2 * h->R * PB_NCHANOUT;
     a.tw2 = h->ft.tw2;
     a.tw3 = h->ft.tw3;
@@ -410,8 +412,9 @@ hipError_t launch_pfb_history(pb_handle *h, int nseg)
 {
     const int nrows = nseg * h->R;
     const int wr = h->hist_rd ^ 1;       // the slot the NEXT batch will read
+    const pb_handle::BufSet &b = h->set();
     dim3 gh(3, 2, h->A);
-    k_pfb_history<<<gh, 256, 0, h->stream>>>(h->d_in, (size_t)h->S * 2 * h->seg_samples, h->seg_samples, h->d_flags,
+    k_pfb_history<<<gh, 256, 0, h->stream>>>(b.d_in, (size_t)h->S * 2 * h->seg_samples, h->seg_samples, b.d_flags,
                                              (size_t)h->S * h->nblk_seg,
                                              h->d_hist_in + (size_t)wr * h->A * 2 * 3 * PFB_HIST_STRIDE,
                                              h->d_hist_flags + (size_t)wr * h->A * 3 * PB_BLK_PER_FFT,

@@ -69,12 +69,13 @@ hipError_t launch_inject_c64(pb_handle *h, int nseg, int inject_now)
     const size_t seg_stride = 2 * pol_stride;
     const size_t ant_stride = (size_t)h->S * seg_stride;
     const float width = h->frb_width;
+    const pb_handle::BufSet &b = h->set();
     dim3 grid((PB_NCHANOUT + 255) / 256, nseg, h->A);
     if (h->cfg.rfi_mode != 1)
-        k_inject_c64<<<grid, 256, 0, h->stream>>>(h->d_Xraw, ant_stride, seg_stride, pol_stride,
+        k_inject_c64<<<grid, 256, 0, h->stream>>>(b.d_Xraw, ant_stride, seg_stride, pol_stride,
                                                   h->d_frb_delays, inject_now, width, h->frb_amp, h->R);
     if (h->cfg.rfi_mode != 0)
-        k_inject_c64<<<grid, 256, 0, h->stream>>>(h->d_Xkur, ant_stride, seg_stride, pol_stride,
+        k_inject_c64<<<grid, 256, 0, h->stream>>>(b.d_Xkur, ant_stride, seg_stride, pol_stride,
                                                   h->d_frb_delays, inject_now, width, h->frb_amp, h->R);
     return hipGetLastError();
 }
@@ -109,16 +110,17 @@ hipError_t launch_detect(pb_handle *h, int nseg, int)
     if (h->cfg.fft_backend == PB_FFT_HIPFFT) {
         // complex spectra -> power planes of the segments just transformed (all antennas at once when
         // the whole handle is processed, else antenna by antenna: planes are [A][S][2][R][...])
+        const pb_handle::BufSet &b = h->set();
         const size_t per_ant = (size_t)nseg * 2 * h->R;
         for (int st = 0; st < 2; ++st) {
             if (st == 0 ? h->cfg.rfi_mode == 1 : h->cfg.rfi_mode == 0) continue;
-            const float2 *X = st ? h->d_Xkur : h->d_Xraw;
-            float *P = st ? h->d_Pkur : h->d_Praw;
+            const float2 *X = st ? b.d_Xkur : b.d_Xraw;
+            float *P = st ? b.d_Pkur : b.d_Praw;
             for (int ant = 0; ant < h->A; ++ant) {
                 const size_t rp0 = (size_t)ant * h->S * 2 * h->R;
                 const size_t nthreads = per_ant * (PB_NCHANOUT / 4);
                 k_power_c64<<<(unsigned)((nthreads + 255) / 256), 256, 0, h->stream>>>(
-                    X + rp0 * PB_NCHAN, P + rp0 * PB_NCHANOUT, h->d_wrow + (size_t)ant * h->S * h->R, per_ant, h->R, st);
+                    X + rp0 * PB_NCHAN, P + rp0 * PB_NCHANOUT, b.d_wrow + (size_t)ant * h->S * h->R, per_ant, h->R, st);
             }
         }
         hipError_t e = hipGetLastError();
@@ -144,7 +146,7 @@ hipError_t launch_coadd_local(pb_handle *h, int nseg, float *d_sum, int accumula
 {
     const int stream = h->cfg.rfi_mode == 0 ? 0 : 1;
     const size_t n = (size_t)nseg * h->ave_per_seg;
-    const float *ave = h->d_ave + (size_t)stream * h->S * h->ave_per_seg;
+    const float *ave = h->set().d_ave + (size_t)stream * h->S * h->ave_per_seg;
     k_coadd_local<<<1024, 256, 0, st>>>(ave, (size_t)2 * h->S * h->ave_per_seg, h->A, d_sum, n,
                                                accumulate);
     return hipGetLastError();

@@ -599,14 +599,15 @@ static void launch_all(const Detect2Args &a, int mode, int npol, int nbit, dim3 
 
 hipError_t launch_detect_pow(pb_handle *h, int nseg)
 {
+    const pb_handle::BufSet &b = h->set();
     Detect2Args a;
-    a.P[0] = h->d_Praw;
-    a.P[1] = h->d_Pkur;
-    a.wrow = h->d_wrow;
+    a.P[0] = b.d_Praw;
+    a.P[1] = b.d_Pkur;
+    a.wrow = b.d_wrow;
     a.bp = h->d_bp;
-    a.codes = h->d_codes;
-    a.ave = h->cfg.keep_ave ? h->d_ave : nullptr;
-    a.ave_target = h->cfg.keep_ave ? h->d_coadd_target : nullptr;
+    a.codes = b.d_codes;
+    a.ave = h->cfg.keep_ave ? b.d_ave : nullptr;
+    a.ave_target = h->cfg.keep_ave ? b.d_coadd_target : nullptr;
     a.target_stream = h->cfg.rfi_mode == 0 ? 0 : 1;
     a.trim = h->trim;
     a.ave_per_seg = h->ave_per_seg;

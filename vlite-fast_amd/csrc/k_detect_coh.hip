@@ -310,13 +310,14 @@ static void launch_coh_all(const DetectCohArgs &a, int mode, int nbit, dim3 grid
 
 hipError_t launch_detect_coh(pb_handle *h, int nseg)
 {
+    const pb_handle::BufSet &b = h->set();
     DetectCohArgs a;
-    a.X[0] = (const float2 *)h->d_Praw;
-    a.X[1] = (const float2 *)h->d_Pkur;
-    a.wrow = h->d_wrow;
+    a.X[0] = (const float2 *)b.d_Praw;
+    a.X[1] = (const float2 *)b.d_Pkur;
+    a.wrow = b.d_wrow;
     a.bp = h->d_bp;
-    a.codes = h->d_codes;
-    a.ave = h->cfg.keep_ave ? h->d_ave : nullptr;
+    a.codes = b.d_codes;
+    a.ave = h->cfg.keep_ave ? b.d_ave : nullptr;
     a.trim = h->trim;
     a.ave_per_seg = h->ave_per_seg;
     a.S = h->S;

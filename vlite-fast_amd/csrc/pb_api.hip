@@ -1,6 +1,9 @@
 // C ABI of libpb_hip.so (include/pb_hip.h): handle lifetime, staging, the per-call kernel
 // sequence that replaces the segment loop body of src/process_baseband.cu:1108-1376, and
 // the D2H side.  No CPU fallback exists: every entry point needs a HIP device.
+// The incoherent sum's entry points (pb_coadd_*) are in pb_coadd.hip, the search's (pb_search_*) in search_*.hip;
+// what they share with this file -- HIPCHK, fail, sync_all, dmalloc, StageTimer, StreamScope -- is in pb_internal.h.
+// Every read of the environment stays in this file.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -10,9 +13,8 @@
 #include "pb_internal.h"
 
 static std::string g_create_err;
-static void drain_timers(pb_handle *h);
 
-static hipError_t sync_all(pb_handle *h)
+hipError_t sync_all(pb_handle *h)
 {
     hipError_t e = hipStreamSynchronize(h->stream);
     if (e == hipSuccess && h->s_det) e = hipStreamSynchronize(h->s_det);
@@ -22,16 +24,7 @@ static hipError_t sync_all(pb_handle *h)
     return e;
 }
 
-#define HIPCHK(h, call)                                                                   \
-    do {                                                                                  \
-        hipError_t e_ = (call);                                                           \
-        if (e_ != hipSuccess) {                                                           \
-            (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                 \
-            return PB_EHIP;                                                               \
-        }                                                                                 \
-    } while (0)
-
-static int fail(pb_handle *h, int code, const std::string &msg)
+int fail(pb_handle *h, int code, const std::string &msg)
 {
     if (h) h->err = msg;
     else g_create_err = msg;
@@ -199,15 +192,6 @@ static int find_dag_bands(pb_handle *h, DagConsts &c)
     return PB_OK;
 }
 
-template <class T>
-static hipError_t dmalloc(pb_handle *h, T **p, size_t n)
-{
-    if (n == 0) { *p = nullptr; return hipSuccess; }
-    hipError_t e = hipMalloc((void **)p, n * sizeof(T));
-    if (e == hipSuccess) h->device_bytes += n * sizeof(T);
-    return e;
-}
-
 static float2 cis_neg(double num, double den)
 {
     const double a = 2.0 * M_PI * num / den;
@@ -269,27 +253,6 @@ static int build_fft_tables(pb_handle *h)
     return PB_OK;
 }
 
-static void store_set(pb_handle *h, int i)
-{
-    pb_handle::BufSet &b = h->sets[i];
-    b.d_in = h->d_in; b.d_flags = h->d_flags; b.d_codes = h->d_codes; b.h_codes = h->h_codes;
-    b.d_wrow = h->d_wrow; b.d_stats = h->d_stats; b.d_fraw = h->d_fraw; b.d_fkur = h->d_fkur;
-    b.d_Praw = h->d_Praw; b.d_Pkur = h->d_Pkur; b.d_ave = h->d_ave; b.d_Xraw = h->d_Xraw; b.d_Xkur = h->d_Xkur;
-    b.d_coadd_target = h->d_coadd_target;
-    b.ev_chan = h->ev_chan; b.ev_det = h->ev_det; b.ev_cl = h->ev_cl; b.processed = h->processed;
-}
-
-static void load_set(pb_handle *h, int i)
-{
-    const pb_handle::BufSet &b = h->sets[i];
-    h->d_in = b.d_in; h->d_flags = b.d_flags; h->d_codes = b.d_codes; h->h_codes = b.h_codes;
-    h->d_wrow = b.d_wrow; h->d_stats = b.d_stats; h->d_fraw = b.d_fraw; h->d_fkur = b.d_fkur;
-    h->d_Praw = b.d_Praw; h->d_Pkur = b.d_Pkur; h->d_ave = b.d_ave; h->d_Xraw = b.d_Xraw; h->d_Xkur = b.d_Xkur;
-    h->d_coadd_target = b.d_coadd_target;
-    h->ev_chan = b.ev_chan; h->ev_det = b.ev_det; h->ev_cl = b.ev_cl; h->processed = b.processed;
-    h->cur_set = i;
-}
-
 // set_frb_delays, src/pb_kernels.cu:338-346; width_rows < 0 selects the reference's 2 ms
 // (frb_width = 2e-3*SEG_PER_SEC*FFTS_PER_SEG with the macro expanded left to right, :1238)
 static int set_frb(pb_handle *h, float dm, float width_rows, float amp)
@@ -345,51 +308,45 @@ static int create_impl(pb_handle *h)
     // second stream, kurtosis + channeliser of the next batch fill the other set.
     h->sets.resize(c.nsets);
     for (int si = 0; si < c.nsets; ++si) {
-    h->d_in = h->d_flags = h->d_codes = h->h_codes = nullptr;
-    h->d_wrow = h->d_stats = h->d_fraw = h->d_fkur = h->d_Praw = h->d_Pkur = h->d_ave = nullptr;
-    h->d_Xraw = h->d_Xkur = nullptr;
-    h->d_coadd_target = nullptr;
-    HIPCHK(h, dmalloc(h, &h->d_in, in_elems + 64));   // + overhang of the channeliser's 16-byte row loads
-    HIPCHK(h, dmalloc(h, &h->d_flags, A * S * h->nblk_seg));
-    HIPCHK(h, hipMemset(h->d_flags, 0, A * S * h->nblk_seg));
-    HIPCHK(h, dmalloc(h, &h->d_wrow, 2 * A * S * R));   // weights, then the rows' flag masks (pb_rowmask)
-    HIPCHK(h, hipMemset(h->d_wrow + A * S * R, 0, A * S * R * sizeof(uint32_t)));
-    {
-        // rfi_mode 0 never computes weights: every row counts fully
-        std::vector<float> ones(A * S * R, 1.0f);
-        HIPCHK(h, hipMemcpy(h->d_wrow, ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice));
+        pb_handle::BufSet &b = h->sets[si];
+        HIPCHK(h, dmalloc(h, &b.d_in, in_elems + 64));   // + overhang of the channeliser's 16-byte row loads
+        HIPCHK(h, dmalloc(h, &b.d_flags, A * S * h->nblk_seg));
+        HIPCHK(h, hipMemset(b.d_flags, 0, A * S * h->nblk_seg));
+        HIPCHK(h, dmalloc(h, &b.d_wrow, 2 * A * S * R));   // weights, then the rows' flag masks (pb_rowmask)
+        HIPCHK(h, hipMemset(b.d_wrow + A * S * R, 0, A * S * R * sizeof(uint32_t)));
+        {
+            // rfi_mode 0 never computes weights: every row counts fully
+            std::vector<float> ones(A * S * R, 1.0f);
+            HIPCHK(h, hipMemcpy(b.d_wrow, ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
+        if (c.debug_keep) HIPCHK(h, dmalloc(h, &b.d_stats, A * 6 * S * h->nblk_seg + A * 5 * S * R));
+        const bool need_raw = c.rfi_mode != 1, need_kur = c.rfi_mode != 0;
+        if (c.fft_backend == PB_FFT_HIPFFT) {
+            if (need_raw) HIPCHK(h, dmalloc(h, &b.d_fraw, in_elems));
+            if (need_kur) HIPCHK(h, dmalloc(h, &b.d_fkur, in_elems));
+            const size_t xn = A * S * 2 * R * PB_NCHAN;
+            if (need_raw) HIPCHK(h, dmalloc(h, &b.d_Xraw, xn));
+            if (need_kur) HIPCHK(h, dmalloc(h, &b.d_Xkur, xn));
+        }
+        {
+            // power planes: written by the LDS channeliser, or from the complex spectra of hipFFT; coherence output:
+            // the complex in-band spectra (float2) in their place
+            const size_t pn = A * S * 2 * R * PB_NCHANOUT * (c.coherence ? 2 : 1);
+            if (need_raw) HIPCHK(h, dmalloc(h, &b.d_Praw, pn));
+            if (need_kur) HIPCHK(h, dmalloc(h, &b.d_Pkur, pn));
+        }
+        HIPCHK(h, dmalloc(h, &b.d_codes, A * 2 * S * h->trim));
+        HIPCHK(h, hipMemset(b.d_codes, 0, A * 2 * S * h->trim));
+        HIPCHK(h, hipHostMalloc((void **)&b.h_codes, A * 2 * S * h->trim, hipHostMallocDefault));
+        memset(b.h_codes, 0, A * 2 * S * h->trim);
+        if (c.keep_ave) {
+            HIPCHK(h, dmalloc(h, &b.d_ave, A * 2 * S * h->ave_per_seg));
+            HIPCHK(h, hipMemset(b.d_ave, 0, A * 2 * S * h->ave_per_seg * sizeof(float)));
+        }
+        HIPCHK(h, hipEventCreateWithFlags(&b.ev_chan, hipEventDisableTiming));
+        HIPCHK(h, hipEventCreateWithFlags(&b.ev_det, hipEventDisableTiming));
+        HIPCHK(h, hipEventCreateWithFlags(&b.ev_cl, hipEventDisableTiming));
     }
-    if (c.debug_keep) HIPCHK(h, dmalloc(h, &h->d_stats, A * 6 * S * h->nblk_seg + A * 5 * S * R));
-    const bool need_raw = c.rfi_mode != 1, need_kur = c.rfi_mode != 0;
-    if (c.fft_backend == PB_FFT_HIPFFT) {
-        if (need_raw) HIPCHK(h, dmalloc(h, &h->d_fraw, in_elems));
-        if (need_kur) HIPCHK(h, dmalloc(h, &h->d_fkur, in_elems));
-        const size_t xn = A * S * 2 * R * PB_NCHAN;
-        if (need_raw) HIPCHK(h, dmalloc(h, &h->d_Xraw, xn));
-        if (need_kur) HIPCHK(h, dmalloc(h, &h->d_Xkur, xn));
-    }
-    {
-        // power planes: written by the LDS channeliser, or from the complex spectra of hipFFT; coherence output:
-        // the complex in-band spectra (float2) in their place
-        const size_t pn = A * S * 2 * R * PB_NCHANOUT * (c.coherence ? 2 : 1);
-        if (need_raw) HIPCHK(h, dmalloc(h, &h->d_Praw, pn));
-        if (need_kur) HIPCHK(h, dmalloc(h, &h->d_Pkur, pn));
-    }
-    HIPCHK(h, dmalloc(h, &h->d_codes, A * 2 * S * h->trim));
-    HIPCHK(h, hipMemset(h->d_codes, 0, A * 2 * S * h->trim));
-    HIPCHK(h, hipHostMalloc((void **)&h->h_codes, A * 2 * S * h->trim, hipHostMallocDefault));
-    memset(h->h_codes, 0, A * 2 * S * h->trim);
-    if (c.keep_ave) {
-        HIPCHK(h, dmalloc(h, &h->d_ave, A * 2 * S * h->ave_per_seg));
-        HIPCHK(h, hipMemset(h->d_ave, 0, A * 2 * S * h->ave_per_seg * sizeof(float)));
-    }
-    HIPCHK(h, hipEventCreateWithFlags(&h->ev_chan, hipEventDisableTiming));
-    HIPCHK(h, hipEventCreateWithFlags(&h->ev_det, hipEventDisableTiming));
-    HIPCHK(h, hipEventCreateWithFlags(&h->ev_cl, hipEventDisableTiming));
-    h->processed = 0;
-    store_set(h, si);
-    }
-    load_set(h, 0);
     if (c.inject_frb) {
         // DM of 80, 2 ms, amplitude 1.05: src/process_baseband.cu:717,1238-1239
         int rc = set_frb(h, 80.f, -1.f, 1.05f);
@@ -410,7 +367,6 @@ static int create_impl(pb_handle *h)
         // window energy per (tap, 500-sample block), from the float taps the kernel multiplies by
         std::vector<float> taps((size_t)4 * PB_NFFT), E(101);
         HIPCHK(h, hipMemcpy(taps.data(), h->ft.taps, taps.size() * sizeof(float), hipMemcpyDeviceToHost));
-        double tot = 0;
         for (int j = 0; j < 4; ++j)
             for (int b = 0; b < PB_BLK_PER_FFT; ++b) {
                 double e = 0;
@@ -422,7 +378,6 @@ static int create_impl(pb_handle *h)
             }
         float totf = 0.f;
         for (int i = 0; i < 100; ++i) totf = totf + E[i];      // same order as k_pfb_weights sums
-        (void)tot;
         E[100] = totf;
         HIPCHK(h, dmalloc(h, &h->d_tapE, (size_t)101));
         HIPCHK(h, hipMemcpy(h->d_tapE, E.data(), 101 * sizeof(float), hipMemcpyHostToDevice));
@@ -507,40 +462,6 @@ extern "C" int pb_create(const pb_config *cfg, pb_handle **out)
         h->trim = (size_t)4 * (h->R / PB_NSCRUNCH) * PB_NCHANOUT * c.nbit / 8;
         h->ave_per_seg = (size_t)4 * (h->R / PB_NSCRUNCH) * PB_NCHANOUT;
     }
-    h->stream = nullptr;
-    h->own_stream = false;
-    h->device_bytes = 0;
-    h->d_in = h->d_vdif = h->d_flags = h->d_codes = nullptr;
-    h->d_frame_idx = nullptr;
-    h->vdif_cap = 0;
-    for (int i = 0; i < 8; ++i) { h->h_frame_idx[i] = nullptr; h->h_idx_cap[i] = 0; h->ev_idx[i] = nullptr; }
-    h->d_wrow = h->d_stats = h->d_fraw = h->d_fkur = h->d_Praw = h->d_Pkur = h->d_bp = h->d_ave = nullptr;
-    h->d_frb_delays = nullptr;
-    h->d_hist_in = h->d_hist_flags = h->d_hist_valid = nullptr;
-    h->hist_rd = 0;
-    h->d_tapE = nullptr;
-    h->d_dag = nullptr;
-    h->frb_width = 0.f;
-    h->frb_amp = 1.f;
-    h->d_Xraw = h->d_Xkur = nullptr;
-    h->h_codes = nullptr;
-    h->ev_chan = h->ev_det = h->ev_cl = nullptr;
-    h->s_coadd = nullptr;
-    h->processed = 0;
-    h->cur_set = 0;
-    h->s_det = nullptr;
-    h->s_copy = nullptr;
-    h->s_kur = nullptr;
-    h->ev_fftdone = h->ev_kur = h->ev_alldone = h->ev_hist = nullptr;
-    h->last_set = -1;
-    h->staged = false;
-    h->d_coadd_target = nullptr;
-    h->d_coadd_codes = h->h_coadd_codes = nullptr;
-    h->ev_coadd[0] = h->ev_coadd[1] = nullptr;
-    h->coadd_slot = h->coadd_last = 0;
-    memset(&h->ft, 0, sizeof h->ft);
-    h->profile = false;
-    memset(&h->timers, 0, sizeof h->timers);
     int rc = create_impl(h);
     if (rc != PB_OK) {
         g_create_err = h->err;
@@ -559,9 +480,7 @@ extern "C" void pb_destroy(pb_handle *h)
     if (h->s_det) (void)hipStreamSynchronize(h->s_det);
     if (h->s_copy) (void)hipStreamSynchronize(h->s_copy);
     for (auto &kv : h->plans) hipfftDestroy(kv.second);
-    bool stored = false;
-    for (auto &b : h->sets) {
-        if (b.d_in == h->d_in) stored = true;
+    for (auto &b : h->sets) {    // (a set pb_create did not finish: what it never allocated is null)
         void *sp[] = {b.d_in, b.d_flags, b.d_codes, b.d_wrow, b.d_stats, b.d_fraw, b.d_fkur,
                       b.d_Praw, b.d_Pkur, b.d_ave, b.d_Xraw, b.d_Xkur};
         for (void *p : sp)
@@ -570,13 +489,6 @@ extern "C" void pb_destroy(pb_handle *h)
         if (b.ev_chan) (void)hipEventDestroy(b.ev_chan);
         if (b.ev_det) (void)hipEventDestroy(b.ev_det);
         if (b.ev_cl) (void)hipEventDestroy(b.ev_cl);
-    }
-    if (!stored) {  // pb_create failed half-way through a set: free the loose members
-        void *sp[] = {h->d_in, h->d_flags, h->d_codes, h->d_wrow, h->d_stats, h->d_fraw, h->d_fkur,
-                      h->d_Praw, h->d_Pkur, h->d_ave, h->d_Xraw, h->d_Xkur};
-        for (void *p : sp)
-            if (p) (void)hipFree(p);
-        if (h->h_codes) (void)hipHostFree(h->h_codes);
     }
     void *ptrs[] = {h->d_vdif, h->d_frame_idx, h->d_bp, h->d_frb_delays, h->d_hist_in, h->d_hist_flags,
                     h->d_hist_valid, h->d_tapE, h->d_dag, h->ft.tw2,
@@ -670,7 +582,7 @@ static hipError_t submit_stream(pb_handle *h, hipStream_t *out)
     // kurtosis pass of the two-kernel path no longer waits for the previous channeliser either).  This set's
     // ev_chan -- its detect is done, queued behind that channeliser and, with taps = 4, behind the history kernel
     // that read the set's last rows -- does, and it completed while the batches in between were being channelised.
-    if (h->processed > 0) return hipStreamWaitEvent(h->s_kur, h->ev_chan, 0);
+    if (h->set().processed > 0) return hipStreamWaitEvent(h->s_kur, h->set().ev_chan, 0);
     return hipSuccess;
 }
 
@@ -740,7 +652,7 @@ extern "C" int pb_submit_planar(pb_handle *h, int ant, int seg, const uint8_t *p
     if (seg < 0 || seg >= h->S) return fail(h, PB_EINVAL, "segment slot out of range");
     if (nsamp != h->seg_samples) return fail(h, PB_EINVAL, "pb_submit_planar: nsamp must equal seg_samples_per_pol");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    uint8_t *dst = h->d_in + (((size_t)ant * h->S + seg) * 2) * h->seg_samples;
+    uint8_t *dst = h->set().d_in + (((size_t)ant * h->S + seg) * 2) * h->seg_samples;
     hipStream_t ss;
     HIPCHK(h, submit_stream(h, &ss));
     HIPCHK(h, hipMemcpyAsync(dst, pol0, nsamp, hipMemcpyHostToDevice, ss));
@@ -755,7 +667,7 @@ extern "C" int pb_submit_planar_dev(pb_handle *h, int ant, int seg, const void *
     if (seg < 0 || seg >= h->S) return fail(h, PB_EINVAL, "segment slot out of range");
     if (nsamp != h->seg_samples) return fail(h, PB_EINVAL, "pb_submit_planar_dev: nsamp must equal seg_samples_per_pol");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    uint8_t *dst = h->d_in + (((size_t)ant * h->S + seg) * 2) * h->seg_samples;
+    uint8_t *dst = h->set().d_in + (((size_t)ant * h->S + seg) * 2) * h->seg_samples;
     hipStream_t ss;
     HIPCHK(h, submit_stream(h, &ss));
     HIPCHK(h, hipMemcpyAsync(dst, pol0, nsamp, hipMemcpyDeviceToDevice, ss));
@@ -822,13 +734,12 @@ extern "C" int pb_submit_vdif_at(pb_handle *h, int ant, int seg0, const uint8_t 
     HIPCHK(h, hipMemcpyAsync(h->d_vdif, block, nbytes, hipMemcpyHostToDevice, ss));
     HIPCHK(h, hipMemcpyAsync(h->d_frame_idx, idx, 2 * nfr * sizeof(int32_t), hipMemcpyHostToDevice, ss));
     HIPCHK(h, hipEventRecord(h->ev_idx[set], ss));
+    hipError_t e;
     {
-        hipStream_t s_main = h->stream;
-        h->stream = ss;
-        hipError_t e = launch_deframe(h, ant, seg0, nfr);
-        h->stream = s_main;
-        HIPCHK(h, e);
+        StreamScope on(h, ss);
+        e = launch_deframe(h, ant, seg0, nfr);
     }
+    HIPCHK(h, e);
     return PB_OK;
 }
 
@@ -845,14 +756,13 @@ extern "C" int pb_input_dev(pb_handle *h, int ant, void **dptr, size_t *nbytes)
 {
     if (!h || !dptr) return PB_EINVAL;
     if (check_ant(h, ant)) return PB_EINVAL;
-    *dptr = h->d_in + (size_t)ant * h->S * 2 * h->seg_samples;
+    *dptr = h->set().d_in + (size_t)ant * h->S * 2 * h->seg_samples;
     if (nbytes) *nbytes = (size_t)h->S * 2 * h->seg_samples;
     return PB_OK;
 }
 
-// Per-stage device time without disturbing the stream: each stage records a pair of events
-// from a pool; pb_get_timers synchronises once and reads them all back.
-static hipEvent_t take_event(pb_handle *h)
+// the event pool of StageTimer (pb_internal.h)
+hipEvent_t take_event(pb_handle *h)
 {
     if (!h->ev_pool.empty()) {
         hipEvent_t e = h->ev_pool.back();
@@ -864,59 +774,32 @@ static hipEvent_t take_event(pb_handle *h)
     return e;
 }
 
+// a finished event pair: its time to the stage's total, both events back to the pool
+static void book_pair(pb_handle *h, const pb_handle::Pending &p)
+{
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
+        h->timers.ms[p.stage] += ms;
+        h->timers.launches[p.stage] += 1;
+    }
+    h->ev_pool.push_back(p.a);
+    h->ev_pool.push_back(p.b);
+}
+
 // Read back the oldest event pairs that have completed, without waiting for anything: keeps the
 // pool small, so that a long profiled run creates no events (hipEventCreate costs tens of us).
-static void retire_done(pb_handle *h)
+void retire_done(pb_handle *h)
 {
     size_t n = 0;
-    while (n < h->pending.size() && hipEventQuery(h->pending[n].b) == hipSuccess) {
-        const auto &p = h->pending[n];
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
-            h->timers.ms[p.stage] += ms;
-            h->timers.launches[p.stage] += 1;
-        }
-        h->ev_pool.push_back(p.a);
-        h->ev_pool.push_back(p.b);
-        ++n;
-    }
+    while (n < h->pending.size() && hipEventQuery(h->pending[n].b) == hipSuccess) book_pair(h, h->pending[n++]);
     if (n) h->pending.erase(h->pending.begin(), h->pending.begin() + n);
 }
 
-struct StageTimer {
-    pb_handle *h;
-    int stage;
-    hipEvent_t a, b;
-    StageTimer(pb_handle *h_, int s) : h(h_), stage(s), a(nullptr), b(nullptr)
-    {
-        if (h->profile) {
-            if (h->ev_pool.size() < 2) retire_done(h);
-            a = take_event(h);
-            b = take_event(h);
-            (void)hipEventRecord(a, h->stream);
-        }
-    }
-    void stop()
-    {
-        if (!h->profile) return;
-        (void)hipEventRecord(b, h->stream);
-        h->pending.push_back({stage, a, b});
-    }
-};
-
-static void drain_timers(pb_handle *h)
+void drain_timers(pb_handle *h)
 {
     if (h->pending.empty()) return;
     (void)sync_all(h);
-    for (auto &p : h->pending) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
-            h->timers.ms[p.stage] += ms;
-            h->timers.launches[p.stage] += 1;
-        }
-        h->ev_pool.push_back(p.a);
-        h->ev_pool.push_back(p.b);
-    }
+    for (const auto &p : h->pending) book_pair(h, p);
     h->pending.clear();
 }
 
@@ -937,13 +820,14 @@ static int exec_fft(pb_handle *h, int nseg)
     }
     const size_t in_ant = (size_t)h->S * 2 * h->seg_samples;
     const size_t x_ant = (size_t)h->S * 2 * h->R * PB_NCHAN;
+    const pb_handle::BufSet &b = h->set();
     for (int a = 0; a < h->A; ++a) {
         if (h->cfg.rfi_mode != 1) {
-            hipfftResult r = hipfftExecR2C(plan, h->d_fraw + a * in_ant, (hipfftComplex *)(h->d_Xraw + a * x_ant));
+            hipfftResult r = hipfftExecR2C(plan, b.d_fraw + a * in_ant, (hipfftComplex *)(b.d_Xraw + a * x_ant));
             if (r != HIPFFT_SUCCESS) return fail(h, PB_EHIP, "hipfftExecR2C failed: " + std::to_string((int)r));
         }
         if (h->cfg.rfi_mode != 0) {
-            hipfftResult r = hipfftExecR2C(plan, h->d_fkur + a * in_ant, (hipfftComplex *)(h->d_Xkur + a * x_ant));
+            hipfftResult r = hipfftExecR2C(plan, b.d_fkur + a * in_ant, (hipfftComplex *)(b.d_Xkur + a * x_ant));
             if (r != HIPFFT_SUCCESS) return fail(h, PB_EHIP, "hipfftExecR2C failed: " + std::to_string((int)r));
         }
     }
@@ -956,12 +840,26 @@ static int check_planes(pb_handle *h)
 {
     const bool hipfft = h->cfg.fft_backend == PB_FFT_HIPFFT;
     const bool need_raw = h->cfg.rfi_mode != 1, need_kur = h->cfg.rfi_mode != 0;
-    bool ok = h->d_in && h->d_flags && h->d_wrow && h->d_codes && h->h_codes && h->d_bp;
-    if (need_raw) ok = ok && h->d_Praw && (!hipfft || (h->d_fraw && h->d_Xraw));
-    if (need_kur) ok = ok && h->d_Pkur && (!hipfft || (h->d_fkur && h->d_Xkur));
-    if (h->cfg.keep_ave) ok = ok && h->d_ave;
+    const pb_handle::BufSet &b = h->set();
+    bool ok = b.d_in && b.d_flags && b.d_wrow && b.d_codes && b.h_codes && h->d_bp;
+    if (need_raw) ok = ok && b.d_Praw && (!hipfft || (b.d_fraw && b.d_Xraw));
+    if (need_kur) ok = ok && b.d_Pkur && (!hipfft || (b.d_fkur && b.d_Xkur));
+    if (h->cfg.keep_ave) ok = ok && b.d_ave;
     if (h->cfg.taps == 4) ok = ok && h->d_hist_in && h->d_hist_flags && h->d_hist_valid && h->d_tapE;
     return ok ? PB_OK : fail(h, PB_ESTATE, "pb_process: a buffer of the selected set is missing for this RFI mode / back end");
+}
+
+// the batch's filterbank bytes of every antenna, of the streams the RFI mode produces, to the set's pinned mirror
+static hipError_t copy_out_codes(pb_handle *h, const pb_handle::BufSet &b, int nseg, hipStream_t st)
+{
+    hipError_t e = hipSuccess;
+    for (int a = 0; a < h->A && e == hipSuccess; ++a)
+        for (int str = 0; str < 2 && e == hipSuccess; ++str) {
+            if (str == 0 ? h->cfg.rfi_mode == 1 : h->cfg.rfi_mode == 0) continue;
+            const size_t o = ((size_t)a * 2 + str) * h->S * h->trim;
+            e = launch_copy_out(h->sched, b.h_codes + o, b.d_codes + o, (size_t)nseg * h->trim, st);
+        }
+    return e;
 }
 
 extern "C" int pb_process(pb_handle *h, int nseg, int inject_now)
@@ -976,7 +874,8 @@ extern "C" int pb_process(pb_handle *h, int nseg, int inject_now)
     // set's previous detect (ev_chan).  The copy-out of that batch's bytes (ev_det) only has to have drained before
     // THIS batch's detect overwrites the code buffer: waiting for it here held the channeliser back by ~0.1 ms per
     // step once the kurtosis pass in front of it was gone (dispatch timeline, profiles/r03_notes.md).
-    HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_chan, 0));
+    pb_handle::BufSet &b = h->set();
+    HIPCHK(h, hipStreamWaitEvent(h->stream, b.ev_chan, 0));
     {
         // The kurtosis pass only needs the raw bytes, and it is a light memory/LDS kernel while
         // detect of the PREVIOUS batch is a latency-bound one that leaves the CUs mostly idle: when
@@ -984,61 +883,59 @@ extern "C" int pb_process(pb_handle *h, int nseg, int inject_now)
         // soon as the previous channeliser has finished, i.e. beside the previous detect.
         const bool fused = pb_fused_kurtosis(h);     // the channeliser flags its own rows: nothing to launch here
         const bool overlap = !fused && !hipfft && h->sets.size() >= 2 && h->last_set >= 0 && h->last_set != h->cur_set;
-        hipStream_t s_main = h->stream;
         hipError_t e = hipSuccess;
-        if (overlap) {
-            // Three or more buffer sets: the kurtosis pass of this batch touches nothing the previous batch's
-            // channeliser uses (another set; the PFB history kernel behind it waits for that channeliser itself),
-            // so it does not wait for that channeliser and runs beside it -- taps = 4: 0.990 -> 0.965 ms per second
-            // of data, the two-kernel taps = 1 path 0.660 -> 0.623 (same box, alternating).  With two sets this
-            // set's flags and weights are still being read by the previous batch's channeliser's successor, detect,
-            // until ev_chan; the wait for the channeliser keeps the kurtosis pass beside that detect.
-            // PB_KUR_EARLY=0 restores the wait.
-            if (!(h->sched.kur_early && h->sets.size() >= 3)) e = hipStreamWaitEvent(h->s_kur, h->ev_fftdone, 0);
-            if (e == hipSuccess) e = hipStreamWaitEvent(h->s_kur, h->ev_chan, 0);  // flags / weights of this set free (its detect is done)
-            h->stream = h->s_kur;
-        } else if (h->sets.size() >= 2 && (h->staged || !fused)) {
-            // staging went to s_kur: the main stream must see it.  (Nothing staged since the last call -- the
-            // caller writes the input buffers itself, pb_input_dev -- and nothing queued on s_kur: no event pair,
-            // a cross-stream dependency costs the command processor ~10-25 us even when it is already met.)
-            e = hipEventRecord(h->ev_kur, h->s_kur);
-            if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->ev_kur, 0);
-        }
-        h->staged = false;
-        if (e == hipSuccess && !fused) {
-            {
-                StageTimer t(h, PB_ST_KURTOSIS);
-                // (PB_SKIP & 4, PB_EXPERIMENTS builds only: only once the set holds the flags of the same input from an
-                //  earlier call -- the experiment re-processes one second of data, and without flags there would be no
-                //  excised transforms either)
-                if (!((pb_skip_mask() & 4) && h->processed > 0)) e = launch_kurtosis_flag(h, nseg, hipfft);
-                t.stop();
+        {
+            StreamScope on(h, overlap ? h->s_kur : h->stream);   // the overlap path: the kurtosis stage goes to s_kur
+            if (overlap) {
+                // Three or more buffer sets: the kurtosis pass of this batch touches nothing the previous batch's
+                // channeliser uses (another set; the PFB history kernel behind it waits for that channeliser itself),
+                // so it does not wait for that channeliser and runs beside it -- taps = 4: 0.990 -> 0.965 ms per second
+                // of data, the two-kernel taps = 1 path 0.660 -> 0.623 (same box, alternating).  With two sets this
+                // set's flags and weights are still being read by the previous batch's channeliser's successor, detect,
+                // until ev_chan; the wait for the channeliser keeps the kurtosis pass beside that detect.
+                // PB_KUR_EARLY=0 restores the wait.
+                if (!(h->sched.kur_early && h->sets.size() >= 3)) e = hipStreamWaitEvent(h->s_kur, h->ev_fftdone, 0);
+                if (e == hipSuccess) e = hipStreamWaitEvent(h->s_kur, b.ev_chan, 0);  // flags / weights of this set free (its detect is done)
+            } else if (h->sets.size() >= 2 && (h->staged || !fused)) {
+                // staging went to s_kur: the main stream must see it.  (Nothing staged since the last call -- the
+                // caller writes the input buffers itself, pb_input_dev -- and nothing queued on s_kur: no event pair,
+                // a cross-stream dependency costs the command processor ~10-25 us even when it is already met.)
+                e = hipEventRecord(h->ev_kur, h->s_kur);
+                if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->ev_kur, 0);
             }
-            // taps = 4: the weights read the flags of the previous batch's last rows (history slot hist_rd, filled by
-            // that batch's history kernel earlier on this stream).
-            // ... or on the main stream, when that batch was not on the overlap path (the first batch, a batch that
-            // repeated its set): ev_hist, recorded behind every history kernel on whichever stream ran it, orders the
-            // weights behind it either way (free when both are on this stream).
-            if (e == hipSuccess && h->cfg.taps == 4) e = hipStreamWaitEvent(h->stream, h->ev_hist, 0);
-            if (e == hipSuccess) e = launch_pfb_weights(h, nseg);
-            if (e == hipSuccess && h->cfg.taps == 4) {
-                // The channeliser only needs what has been queued up to here: release it now.  Then keep this
-                // batch's last three rows and flags for the next one in the OTHER history slot -- the one the
-                // previous batch's channeliser reads, hence behind it (ev_fftdone still holds its record); the next
-                // batch's weights and staging follow on this stream, its channeliser behind them.  (Round 2 ran the
-                // history kernel behind the channeliser on the main stream and the next weights behind THAT: two
-                // cross-stream hand-overs between consecutive channelisers.)
-                if (overlap) e = hipEventRecord(h->ev_kur, h->s_kur);
-                if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->ev_fftdone, 0);
-                if (e == hipSuccess) e = launch_pfb_history(h, nseg);
-                if (e == hipSuccess) e = hipEventRecord(h->ev_hist, h->stream);
+            h->staged = false;
+            if (e == hipSuccess && !fused) {
+                {
+                    StageTimer t(h, PB_ST_KURTOSIS);
+                    // (PB_SKIP & 4, PB_EXPERIMENTS builds only: only once the set holds the flags of the same input from an
+                    //  earlier call -- the experiment re-processes one second of data, and without flags there would be no
+                    //  excised transforms either)
+                    if (!((pb_skip_mask() & 4) && b.processed > 0)) e = launch_kurtosis_flag(h, nseg, hipfft);
+                    t.stop();
+                }
+                // taps = 4: the weights read the flags of the previous batch's last rows (history slot hist_rd, filled by
+                // that batch's history kernel earlier on this stream).
+                // ... or on the main stream, when that batch was not on the overlap path (the first batch, a batch that
+                // repeated its set): ev_hist, recorded behind every history kernel on whichever stream ran it, orders the
+                // weights behind it either way (free when both are on this stream).
+                if (e == hipSuccess && h->cfg.taps == 4) e = hipStreamWaitEvent(h->stream, h->ev_hist, 0);
+                if (e == hipSuccess) e = launch_pfb_weights(h, nseg);
+                if (e == hipSuccess && h->cfg.taps == 4) {
+                    // The channeliser only needs what has been queued up to here: release it now.  Then keep this
+                    // batch's last three rows and flags for the next one in the OTHER history slot -- the one the
+                    // previous batch's channeliser reads, hence behind it (ev_fftdone still holds its record); the next
+                    // batch's weights and staging follow on this stream, its channeliser behind them.  (Round 2 ran the
+                    // history kernel behind the channeliser on the main stream and the next weights behind THAT: two
+                    // cross-stream hand-overs between consecutive channelisers.)
+                    if (overlap) e = hipEventRecord(h->ev_kur, h->s_kur);
+                    if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->ev_fftdone, 0);
+                    if (e == hipSuccess) e = launch_pfb_history(h, nseg);
+                    if (e == hipSuccess) e = hipEventRecord(h->ev_hist, h->stream);
+                }
             }
+            if (overlap && e == hipSuccess && h->cfg.taps != 4) e = hipEventRecord(h->ev_kur, h->s_kur);
         }
-        if (overlap) {
-            if (e == hipSuccess && h->cfg.taps != 4) e = hipEventRecord(h->ev_kur, h->s_kur);
-            h->stream = s_main;
-            if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->ev_kur, 0);
-        }
+        if (overlap && e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->ev_kur, 0);
         HIPCHK(h, e);
     }
     if (hipfft) {
@@ -1066,54 +963,42 @@ extern "C" int pb_process(pb_handle *h, int nseg, int inject_now)
     // ~9 % shorter than back to back (0.915 vs 1.007 ms per second of data; PB_OVERLAP_DETECT=0 turns
     // it off).  With one buffer set everything stays on one stream.
     if (h->sched.overlap_detect && h->sets.size() >= 2 && !hipfft) {
-        hipStream_t s_main = h->stream;
         hipError_t e2 = hipStreamWaitEvent(h->s_det, h->ev_fftdone, 0);
-        if (e2 == hipSuccess) e2 = hipStreamWaitEvent(h->s_det, h->ev_det, 0);  // this set's previous bytes have left
-        if (e2 == hipSuccess) e2 = hipStreamWaitEvent(h->s_det, h->ev_cl, 0);   // planes of this set were summed
-        h->stream = h->s_det;
-        if (e2 == hipSuccess) {
-            StageTimer t(h, PB_ST_DETECT);
-            if (!(pb_skip_mask() & 2)) e2 = launch_detect(h, nseg, inject_now);
-            t.stop();
-        }
-        if (e2 == hipSuccess) e2 = hipEventRecord(h->ev_chan, h->s_det);   // this set's kernels are done
-        // the copy-out has a stream of its own: behind detect on s_det it would hold up the next batch's
-        // detect whenever it is slow (many antennas, few copy workgroups)
-        if (e2 == hipSuccess) e2 = hipStreamWaitEvent(h->s_copy, h->ev_chan, 0);
-        for (int a = 0; a < h->A && e2 == hipSuccess; ++a)
-            for (int st = 0; st < 2 && e2 == hipSuccess; ++st) {
-                if (st == 0 ? h->cfg.rfi_mode == 1 : h->cfg.rfi_mode == 0) continue;
-                const size_t o = ((size_t)a * 2 + st) * h->S * h->trim;
-                e2 = launch_copy_out(h->sched, h->h_codes + o, h->d_codes + o, (size_t)nseg * h->trim, h->s_copy);
+        if (e2 == hipSuccess) e2 = hipStreamWaitEvent(h->s_det, b.ev_det, 0);  // this set's previous bytes have left
+        if (e2 == hipSuccess) e2 = hipStreamWaitEvent(h->s_det, b.ev_cl, 0);   // planes of this set were summed
+        {
+            StreamScope on(h, h->s_det);
+            if (e2 == hipSuccess) {
+                StageTimer t(h, PB_ST_DETECT);
+                if (!(pb_skip_mask() & 2)) e2 = launch_detect(h, nseg, inject_now);
+                t.stop();
             }
-        if (e2 == hipSuccess) e2 = hipEventRecord(h->ev_det, h->s_copy);
-        if (e2 == hipSuccess) e2 = hipEventRecord(h->ev_alldone, h->s_copy);
-        h->stream = s_main;
+            if (e2 == hipSuccess) e2 = hipEventRecord(b.ev_chan, h->s_det);   // this set's kernels are done
+            // the copy-out has a stream of its own: behind detect on s_det it would hold up the next batch's
+            // detect whenever it is slow (many antennas, few copy workgroups)
+            if (e2 == hipSuccess) e2 = hipStreamWaitEvent(h->s_copy, b.ev_chan, 0);
+            if (e2 == hipSuccess) e2 = copy_out_codes(h, b, nseg, h->s_copy);
+            if (e2 == hipSuccess) e2 = hipEventRecord(b.ev_det, h->s_copy);
+            if (e2 == hipSuccess) e2 = hipEventRecord(h->ev_alldone, h->s_copy);
+        }
         HIPCHK(h, e2);
-        h->processed = nseg;
-        h->sets[h->cur_set].processed = nseg;
+        b.processed = nseg;
         return PB_OK;
     }
     {
-        HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_det, 0));  // this set's previous bytes have left
-        HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_cl, 0));   // planes of this set were summed
+        HIPCHK(h, hipStreamWaitEvent(h->stream, b.ev_det, 0));  // this set's previous bytes have left
+        HIPCHK(h, hipStreamWaitEvent(h->stream, b.ev_cl, 0));   // planes of this set were summed
         StageTimer t(h, PB_ST_DETECT);
         HIPCHK(h, launch_detect(h, nseg, inject_now));
         t.stop();
     }
-    HIPCHK(h, hipEventRecord(h->ev_chan, h->stream));
+    HIPCHK(h, hipEventRecord(b.ev_chan, h->stream));
     HIPCHK(h, hipEventRecord(h->ev_alldone, h->stream));
-    hipError_t e = hipStreamWaitEvent(h->s_det, h->ev_chan, 0);
-    for (int a = 0; a < h->A && e == hipSuccess; ++a)
-        for (int st = 0; st < 2 && e == hipSuccess; ++st) {
-            if (st == 0 ? h->cfg.rfi_mode == 1 : h->cfg.rfi_mode == 0) continue;
-            const size_t o = ((size_t)a * 2 + st) * h->S * h->trim;
-            e = launch_copy_out(h->sched, h->h_codes + o, h->d_codes + o, (size_t)nseg * h->trim, h->s_det);
-        }
-    if (e == hipSuccess) e = hipEventRecord(h->ev_det, h->s_det);
+    hipError_t e = hipStreamWaitEvent(h->s_det, b.ev_chan, 0);
+    if (e == hipSuccess) e = copy_out_codes(h, b, nseg, h->s_det);
+    if (e == hipSuccess) e = hipEventRecord(b.ev_det, h->s_det);
     HIPCHK(h, e);
-    h->processed = nseg;
-    h->sets[h->cur_set].processed = nseg;
+    b.processed = nseg;
     return PB_OK;
 }
 
@@ -1131,8 +1016,7 @@ extern "C" int pb_select_set(pb_handle *h, int set)
 {
     if (!h) return PB_EINVAL;
     if (set < 0 || set >= (int)h->sets.size()) return fail(h, PB_EINVAL, "pb_select_set: no such buffer set");
-    store_set(h, h->cur_set);
-    load_set(h, set);
+    h->cur_set = set;
     return PB_OK;
 }
 
@@ -1142,8 +1026,9 @@ extern "C" int pb_fetch_ptr(pb_handle *h, int ant, int stream, const uint8_t **c
     if (check_ant(h, ant)) return PB_EINVAL;
     if (stream < 0 || stream > 1) return fail(h, PB_EINVAL, "stream must be 0 or 1");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipEventSynchronize(h->ev_det));
-    *codes = h->h_codes + ((size_t)ant * 2 + stream) * h->S * h->trim;
+    const pb_handle::BufSet &b = h->set();
+    HIPCHK(h, hipEventSynchronize(b.ev_det));
+    *codes = b.h_codes + ((size_t)ant * 2 + stream) * h->S * h->trim;
     return PB_OK;
 }
 
@@ -1157,26 +1042,27 @@ extern "C" int pb_fetch(pb_handle *h, int ant, int seg0, int nseg, uint8_t *raw_
     HIPCHK(h, hipSetDevice(h->cfg.device));
     // the selected set's detect + asynchronous D2H (pinned mirror h_codes) have an event of
     // their own, so fetching one set does not wait for work in flight on the other
-    HIPCHK(h, hipEventSynchronize(h->ev_det));
+    const pb_handle::BufSet &b = h->set();
+    HIPCHK(h, hipEventSynchronize(b.ev_det));
     const size_t S = h->S;
-    const uint8_t *c0 = h->h_codes + (((size_t)ant * 2 + 0) * S + seg0) * h->trim;
-    const uint8_t *c1 = h->h_codes + (((size_t)ant * 2 + 1) * S + seg0) * h->trim;
+    const uint8_t *c0 = b.h_codes + (((size_t)ant * 2 + 0) * S + seg0) * h->trim;
+    const uint8_t *c1 = b.h_codes + (((size_t)ant * 2 + 1) * S + seg0) * h->trim;
     if (raw_codes) memcpy(raw_codes, c0, (size_t)nseg * h->trim);
     if (kur_codes) memcpy(kur_codes, c1, (size_t)nseg * h->trim);
-    if (ave_raw) HIPCHK(h, hipMemcpy(ave_raw, h->d_ave + (((size_t)ant * 2 + 0) * S + seg0) * h->ave_per_seg,
+    if (ave_raw) HIPCHK(h, hipMemcpy(ave_raw, b.d_ave + (((size_t)ant * 2 + 0) * S + seg0) * h->ave_per_seg,
                                     (size_t)nseg * h->ave_per_seg * sizeof(float), hipMemcpyDeviceToHost));
     const int cstream = h->cfg.rfi_mode == 0 ? 0 : 1;     // the stream whose plane a coadd target replaces
-    if (h->d_coadd_target && ant == 0 && ((cstream == 0 && ave_raw) || (cstream == 1 && ave_kur))) {
-        HIPCHK(h, hipMemcpy(cstream ? ave_kur : ave_raw, h->d_coadd_target + (size_t)seg0 * h->ave_per_seg,
+    if (b.d_coadd_target && ant == 0 && ((cstream == 0 && ave_raw) || (cstream == 1 && ave_kur))) {
+        HIPCHK(h, hipMemcpy(cstream ? ave_kur : ave_raw, b.d_coadd_target + (size_t)seg0 * h->ave_per_seg,
                             (size_t)nseg * h->ave_per_seg * sizeof(float), hipMemcpyDeviceToHost));
         if (cstream) ave_kur = nullptr; else ave_raw = nullptr;
     }
-    if (ave_kur) HIPCHK(h, hipMemcpy(ave_kur, h->d_ave + (((size_t)ant * 2 + 1) * S + seg0) * h->ave_per_seg,
+    if (ave_kur) HIPCHK(h, hipMemcpy(ave_kur, b.d_ave + (((size_t)ant * 2 + 1) * S + seg0) * h->ave_per_seg,
                                     (size_t)nseg * h->ave_per_seg * sizeof(float), hipMemcpyDeviceToHost));
     if (weights) {
         // what tscrunch_weights sees: after pscrunch_weights (npol 1) rows below MIN_WEIGHT are 0
         std::vector<float> w((size_t)nseg * h->R);
-        HIPCHK(h, hipMemcpy(w.data(), h->d_wrow + (size_t)ant * S * h->R + (size_t)seg0 * h->R,
+        HIPCHK(h, hipMemcpy(w.data(), b.d_wrow + (size_t)ant * S * h->R + (size_t)seg0 * h->R,
                             w.size() * sizeof(float), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < w.size(); ++i) {
             float v = w[i];
@@ -1192,280 +1078,12 @@ extern "C" int pb_output_dev(pb_handle *h, int ant, int stream, void **codes, vo
     if (!h) return PB_EINVAL;
     if (check_ant(h, ant)) return PB_EINVAL;
     if (stream < 0 || stream > 1) return fail(h, PB_EINVAL, "stream must be 0 or 1");
-    if (codes) *codes = h->d_codes + ((size_t)ant * 2 + stream) * h->S * h->trim;
+    const pb_handle::BufSet &b = h->set();
+    if (codes) *codes = b.d_codes + ((size_t)ant * 2 + stream) * h->S * h->trim;
     if (ave) {
-        *ave = h->d_ave ? h->d_ave + ((size_t)ant * 2 + stream) * h->S * h->ave_per_seg : nullptr;
-        if (h->d_coadd_target && ant == 0 && stream == (h->cfg.rfi_mode == 0 ? 0 : 1)) *ave = h->d_coadd_target;
+        *ave = b.d_ave ? b.d_ave + ((size_t)ant * 2 + stream) * h->S * h->ave_per_seg : nullptr;
+        if (b.d_coadd_target && ant == 0 && stream == (h->cfg.rfi_mode == 0 ? 0 : 1)) *ave = b.d_coadd_target;
     }
-    return PB_OK;
-}
-
-extern "C" int pb_set_coadd_stream(pb_handle *h, void *stream)
-{
-    if (!h) return PB_EINVAL;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, sync_all(h));
-    h->s_coadd = (hipStream_t)stream;
-    return PB_OK;
-}
-
-// The incoherent sum is defined on the one-pol (AA+BB) planes: coherence output does not take part in it.
-static int no_coherence(pb_handle *h, const char *what)
-{
-    if (!h->cfg.coherence) return PB_OK;
-    return fail(h, PB_EINVAL, std::string(what) + ": the coadd entry points do not take coherence output (npol = 1 only)");
-}
-
-extern "C" int pb_coadd_local(pb_handle *h, int nseg, float *d_sum, int accumulate)
-{
-    if (!h || !d_sum) return PB_EINVAL;
-    if (int rc = no_coherence(h, "pb_coadd_local")) return rc;
-    if (!h->cfg.keep_ave) return fail(h, PB_ESTATE, "pb_coadd_local needs keep_ave=1");
-    if (nseg < 1 || nseg > h->S) return fail(h, PB_EINVAL, "pb_coadd_local: nseg out of range");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    // The fp32 planes come from this set's detect, which may have run on the second stream.  On a
-    // coadd stream of its own (pb_set_coadd_stream) this wait holds up neither the next batch's
-    // channeliser nor its detect.
-    hipStream_t cs = h->s_coadd ? h->s_coadd : h->stream;
-    // The planes come from this set's detect, which runs on another stream.  When the host already knows that it
-    // has finished (e.g. the batch's bytes have been fetched), no device-side wait is queued: a pending
-    // cross-stream wait on that event was measured to cost the whole pipeline 0.12 ms per second of data.
-    if (hipEventQuery(h->ev_chan) != hipSuccess) HIPCHK(h, hipStreamWaitEvent(cs, h->ev_chan, 0));
-    if (h->d_coadd_target && d_sum == h->d_coadd_target && !accumulate) {
-        // nant = 1 with a coadd target: detect wrote the plane into d_sum itself.  Nothing to launch; the
-        // "planes consumed" event is recorded by pb_coadd_release, after the caller's collective.
-        if (nseg > h->processed) return fail(h, PB_EINVAL, "pb_coadd_local: more segments than the batch holds");
-        return PB_OK;
-    }
-    hipStream_t s_main = h->stream;
-    h->stream = cs;                       // (StageTimer records on h->stream)
-    hipError_t e;
-    {
-        StageTimer t(h, PB_ST_COADD);
-        e = launch_coadd_local(h, nseg, d_sum, accumulate, cs);
-        t.stop();
-    }
-    if (e == hipSuccess) e = hipEventRecord(h->ev_cl, cs);
-    h->stream = s_main;
-    HIPCHK(h, e);
-    return PB_OK;
-}
-
-// The same local sum taken from this batch's quantised codes (coadd_codes.hip): what a coadder fed from the co
-// rings has to work with.  Needs no fp32 planes (keep_ave may be 0).
-hipError_t launch_coadd_local_codes(pb_handle *h, int nseg, float *d_sum, int accumulate, hipStream_t st);
-extern "C" int pb_coadd_local_codes(pb_handle *h, int nseg, float *d_sum, int accumulate)
-{
-    if (!h || !d_sum) return PB_EINVAL;
-    if (int rc = no_coherence(h, "pb_coadd_local_codes")) return rc;
-    if (nseg < 1 || nseg > h->S) return fail(h, PB_EINVAL, "pb_coadd_local_codes: nseg out of range");
-    if (nseg > h->processed) return fail(h, PB_EINVAL, "pb_coadd_local_codes: more segments than the batch holds");
-    if (h->d_coadd_target && d_sum == h->d_coadd_target)
-        return fail(h, PB_ESTATE, "pb_coadd_local_codes: d_sum is the set's fp32 coadd target");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t cs = h->s_coadd ? h->s_coadd : h->stream;
-    if (hipEventQuery(h->ev_chan) != hipSuccess) HIPCHK(h, hipStreamWaitEvent(cs, h->ev_chan, 0));
-    hipError_t e = launch_coadd_local_codes(h, nseg, d_sum, accumulate, cs);
-    if (e == hipSuccess) e = hipEventRecord(h->ev_cl, cs);      // (the set's next detect writes codes and planes alike)
-    HIPCHK(h, e);
-    return PB_OK;
-}
-
-// leaves of S over items[0..n) left to right: the even positions' subtree, then the odd positions'
-static void tree_order_rec(const int32_t *items, int n, int32_t *&out)
-{
-    if (n <= 1) {
-        if (n == 1) *out++ = items[0];
-        return;
-    }
-    int32_t ev[PB_COADD_MAX_LEAVES], od[PB_COADD_MAX_LEAVES];
-    int ne = 0, no = 0;
-    for (int i = 0; i < n; ++i) (i & 1 ? od[no++] : ev[ne++]) = items[i];
-    tree_order_rec(ev, ne, out);
-    tree_order_rec(od, no, out);
-}
-
-extern "C" int pb_coadd_tree_order(int n, int32_t *order)
-{
-    if (!order || n < 1 || n > PB_COADD_MAX_LEAVES) return PB_EINVAL;
-    int32_t items[PB_COADD_MAX_LEAVES];
-    for (int i = 0; i < n; ++i) items[i] = i;
-    int32_t *out = order;
-    tree_order_rec(items, n, out);
-    return PB_OK;
-}
-
-// The incoherent sum in the defined order (coadd_tree.hip): one rank's node of the tree from
-// the selected set's fp32 planes, ordered against detect and the set's next batch exactly like pb_coadd_local.
-extern "C" int pb_coadd_local_tree(pb_handle *h, int nseg, const int32_t *ant_order, int n, float *d_dst)
-{
-    if (!h || !d_dst || !ant_order) return PB_EINVAL;
-    if (int rc = no_coherence(h, "pb_coadd_local_tree")) return rc;
-    if (!h->cfg.keep_ave) return fail(h, PB_ESTATE, "pb_coadd_local_tree needs keep_ave=1");
-    if (nseg < 1 || nseg > h->S) return fail(h, PB_EINVAL, "pb_coadd_local_tree: nseg out of range");
-    if (nseg > h->processed) return fail(h, PB_EINVAL, "pb_coadd_local_tree: more segments than the batch holds");
-    if (n < 1 || n > PB_COADD_MAX_LEAVES) return fail(h, PB_EINVAL, "pb_coadd_local_tree: 1..PB_COADD_MAX_LEAVES leaves");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int stream = h->cfg.rfi_mode == 0 ? 0 : 1;
-    const float *leaves[PB_COADD_MAX_LEAVES];
-    for (int i = 0; i < n; ++i) {
-        const int a = ant_order[i];
-        if (a < 0 || a >= h->A) return fail(h, PB_EINVAL, "pb_coadd_local_tree: antenna index out of range");
-        leaves[i] = (h->d_coadd_target && a == 0) ? h->d_coadd_target
-                                                  : h->d_ave + ((size_t)a * 2 + stream) * h->S * h->ave_per_seg;
-        if (leaves[i] == d_dst && n > 1) return fail(h, PB_EINVAL, "pb_coadd_local_tree: d_dst is one of the leaves");
-    }
-    hipStream_t cs = h->s_coadd ? h->s_coadd : h->stream;
-    if (hipEventQuery(h->ev_chan) != hipSuccess) HIPCHK(h, hipStreamWaitEvent(cs, h->ev_chan, 0));
-    if (n == 1 && leaves[0] == d_dst) return PB_OK;       // (a coadd target: detect wrote the leaf where it is wanted;
-                                                          //  pb_coadd_release books the "planes consumed" event)
-    hipStream_t s_main = h->stream;
-    h->stream = cs;                       // (StageTimer records on h->stream)
-    hipError_t e;
-    {
-        StageTimer t(h, PB_ST_COADD);
-        e = launch_coadd_tree(leaves, n, d_dst, (size_t)nseg * h->ave_per_seg, cs);
-        t.stop();
-    }
-    if (e == hipSuccess) e = hipEventRecord(h->ev_cl, cs);
-    h->stream = s_main;
-    HIPCHK(h, e);
-    return PB_OK;
-}
-
-// The root's part: T_n over the gathered partial sums (caller-owned planes), on the coadd stream.
-extern "C" int pb_coadd_tree(pb_handle *h, const float *const *d_leaves, int n, float *d_dst, size_t nfloat)
-{
-    if (!h || !d_leaves || !d_dst) return PB_EINVAL;
-    if (int rc = no_coherence(h, "pb_coadd_tree")) return rc;
-    if (n < 1 || n > PB_COADD_MAX_LEAVES) return fail(h, PB_EINVAL, "pb_coadd_tree: 1..PB_COADD_MAX_LEAVES leaves");
-    if (nfloat & 3) return fail(h, PB_EINVAL, "pb_coadd_tree: nfloat must be a multiple of 4");
-    for (int i = 0; i < n; ++i) {
-        if (!d_leaves[i] || ((uintptr_t)d_leaves[i] & 15)) return fail(h, PB_EINVAL, "pb_coadd_tree: leaf null or not 16-byte aligned");
-        if (d_leaves[i] == d_dst && n > 1) return fail(h, PB_EINVAL, "pb_coadd_tree: d_dst is one of the leaves");
-    }
-    if ((uintptr_t)d_dst & 15) return fail(h, PB_EINVAL, "pb_coadd_tree: d_dst not 16-byte aligned");
-    if (n == 1 && d_leaves[0] == d_dst) return PB_OK;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t cs = h->s_coadd ? h->s_coadd : h->stream;
-    hipStream_t s_main = h->stream;
-    h->stream = cs;
-    hipError_t e;
-    {
-        StageTimer t(h, PB_ST_COADD);
-        e = launch_coadd_tree(d_leaves, n, d_dst, nfloat, cs);
-        t.stop();
-    }
-    h->stream = s_main;
-    HIPCHK(h, e);
-    return PB_OK;
-}
-
-extern "C" int pb_set_coadd_target(pb_handle *h, float *d_sum)
-{
-    if (!h) return PB_EINVAL;
-    if (int rc = no_coherence(h, "pb_set_coadd_target")) return rc;
-    if (d_sum && (h->A != 1 || !h->cfg.keep_ave || h->cfg.fft_backend != PB_FFT_LDS))
-        return fail(h, PB_ESTATE, "pb_set_coadd_target needs nant=1, keep_ave=1 and the LDS back end");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, sync_all(h));              // no detect of this handle is writing a plane
-    h->d_coadd_target = d_sum;
-    return PB_OK;
-}
-
-extern "C" int pb_coadd_release(pb_handle *h)
-{
-    if (!h) return PB_EINVAL;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t cs = h->s_coadd ? h->s_coadd : h->stream;
-    HIPCHK(h, hipEventRecord(h->ev_cl, cs));      // what the set's next detect waits for before it writes the planes
-    return PB_OK;
-}
-
-// the two pinned / device slots the coadded bytes alternate between (allocated on first use)
-static int coadd_slots(pb_handle *h)
-{
-    const size_t nb = (size_t)h->S * h->trim;
-    if (!h->d_coadd_codes) {
-        HIPCHK(h, dmalloc(h, &h->d_coadd_codes, 2 * nb));
-        HIPCHK(h, hipHostMalloc((void **)&h->h_coadd_codes, 2 * nb, hipHostMallocDefault));
-        for (int i = 0; i < 2; ++i) HIPCHK(h, hipEventCreateWithFlags(&h->ev_coadd[i], hipEventDisableTiming));
-        h->coadd_slot = 0;
-    }
-    return PB_OK;
-}
-
-// Root side of the incoherent sum: scale by 1/sqrt(N), requantise on the GPU, bring the bytes to
-// pinned host memory asynchronously.  codes_host != NULL: wait and copy out (simple, blocking).
-// codes_host == NULL: return at once; the bytes of call k are read with pb_coadd_fetch_ptr after
-// later work has been queued (two pinned buffers alternate), so the root does not stall per batch.
-extern "C" int pb_coadd_finish(pb_handle *h, int nseg, const float *d_sum, int nant_total, uint8_t *codes_host)
-{
-    if (!h || !d_sum || nant_total < 1) return PB_EINVAL;
-    if (int rc = no_coherence(h, "pb_coadd_finish")) return rc;
-    if (nseg < 1 || nseg > h->S) return fail(h, PB_EINVAL, "pb_coadd_finish: nseg out of range");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t nb = (size_t)h->S * h->trim;
-    if (int rc = coadd_slots(h)) return rc;
-    const int slot = h->coadd_slot;
-    h->coadd_slot ^= 1;
-    h->coadd_last = slot;
-    const float scale = (float)(1.0 / sqrt((double)nant_total));
-    // requantise and copy out on the coadd stream, in order (the slot's previous copy-out, two calls
-    // ago, went through the same stream)
-    hipStream_t cs = h->s_coadd ? h->s_coadd : h->stream;
-    HIPCHK(h, launch_coadd_digitise(h, nseg, d_sum, scale, h->d_coadd_codes + slot * nb, cs));
-    HIPCHK(h, launch_copy_out(h->sched, h->h_coadd_codes + slot * nb, h->d_coadd_codes + slot * nb, (size_t)nseg * h->trim, cs));
-    HIPCHK(h, hipEventRecord(h->ev_coadd[slot], cs));
-    if (codes_host) {
-        HIPCHK(h, hipEventSynchronize(h->ev_coadd[slot]));
-        memcpy(codes_host, h->h_coadd_codes + slot * nb, (size_t)nseg * h->trim);
-    }
-    return PB_OK;
-}
-
-// One rank's slice of the ordered sum, requantised where it was summed (coadd.py, "sliced" layout).
-extern "C" int pb_coadd_digitise(pb_handle *h, const float *d_sum, size_t nfloat, int nant_total, uint8_t *d_codes)
-{
-    if (!h || !d_sum || !d_codes || nant_total < 1) return PB_EINVAL;
-    if (int rc = no_coherence(h, "pb_coadd_digitise")) return rc;
-    if (h->cfg.npol != 1) return fail(h, PB_ESTATE, "pb_coadd_digitise: a flat plane range is a code range only with npol = 1");
-    if (nfloat == 0 || (nfloat & 7)) return fail(h, PB_EINVAL, "pb_coadd_digitise: nfloat must be a positive multiple of 8");
-    if (((uintptr_t)d_sum & 15) || ((uintptr_t)d_codes & 3)) return fail(h, PB_EINVAL, "pb_coadd_digitise: misaligned buffer");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t cs = h->s_coadd ? h->s_coadd : h->stream;
-    const float scale = (float)(1.0 / sqrt((double)nant_total));
-    HIPCHK(h, launch_coadd_digitise_flat(h, d_sum, nfloat, scale, d_codes, cs));
-    return PB_OK;
-}
-
-// The batch's coadded bytes, assembled on the device by the caller, to the pinned buffer pb_coadd_fetch_ptr hands out.
-extern "C" int pb_coadd_publish(pb_handle *h, const uint8_t *d_codes, size_t nbytes)
-{
-    if (!h || !d_codes) return PB_EINVAL;
-    if (int rc = no_coherence(h, "pb_coadd_publish")) return rc;
-    const size_t nb = (size_t)h->S * h->trim;
-    if (nbytes == 0 || nbytes > nb) return fail(h, PB_EINVAL, "pb_coadd_publish: more bytes than a batch holds");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (int rc = coadd_slots(h)) return rc;
-    const int slot = h->coadd_slot;
-    h->coadd_slot ^= 1;
-    h->coadd_last = slot;
-    hipStream_t cs = h->s_coadd ? h->s_coadd : h->stream;
-    HIPCHK(h, launch_copy_out(h->sched, h->h_coadd_codes + slot * nb, d_codes, nbytes, cs));
-    HIPCHK(h, hipEventRecord(h->ev_coadd[slot], cs));
-    return PB_OK;
-}
-
-extern "C" int pb_coadd_fetch_ptr(pb_handle *h, int age, const uint8_t **codes)
-{
-    if (!h || !codes) return PB_EINVAL;
-    if (!h->d_coadd_codes) return fail(h, PB_ESTATE, "pb_coadd_fetch_ptr: no pb_coadd_finish yet");
-    if (age < 0 || age > 1) return fail(h, PB_EINVAL, "pb_coadd_fetch_ptr: age must be 0 (latest) or 1 (previous)");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int slot = age == 0 ? h->coadd_last : (h->coadd_last ^ 1);
-    HIPCHK(h, hipEventSynchronize(h->ev_coadd[slot]));
-    *codes = h->h_coadd_codes + (size_t)slot * h->S * h->trim;
     return PB_OK;
 }
 
@@ -1503,19 +1121,20 @@ extern "C" int pb_debug_fetch(pb_handle *h, int what, int ant, int seg, void *ds
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, sync_all(h));
     const size_t nb = h->nblk_seg, cap = (size_t)h->S * nb;
+    const pb_handle::BufSet &b = h->set();
     if (what == PB_DBG_POW || what == PB_DBG_KUR || what == PB_DBG_DAG) {
-        if (!h->d_stats) return fail(h, PB_ESTATE, "pb_debug_fetch: statistics need debug_keep=1");
+        if (!b.d_stats) return fail(h, PB_ESTATE, "pb_debug_fetch: statistics need debug_keep=1");
         if (nbytes != 2 * nb * sizeof(float)) return fail(h, PB_EINVAL, "pb_debug_fetch: size");
         for (int pol = 0; pol < 2; ++pol) {
-            const float *src = h->d_stats + (size_t)ant * 6 * cap + ((size_t)what * 2 + pol) * cap + (size_t)seg * nb;
+            const float *src = b.d_stats + (size_t)ant * 6 * cap + ((size_t)what * 2 + pol) * cap + (size_t)seg * nb;
             HIPCHK(h, hipMemcpy((float *)dst + pol * nb, src, nb * sizeof(float), hipMemcpyDeviceToHost));
         }
         return PB_OK;
     }
     if (what == PB_DBG_POW_FB || what == PB_DBG_KUR_FB || what == PB_DBG_DAG_FB) {
-        if (!h->d_stats) return fail(h, PB_ESTATE, "pb_debug_fetch: statistics need debug_keep=1");
+        if (!b.d_stats) return fail(h, PB_ESTATE, "pb_debug_fetch: statistics need debug_keep=1");
         const size_t rcap = (size_t)h->S * h->R;
-        const float *fb = h->d_stats + (size_t)h->A * 6 * cap + (size_t)ant * 5 * rcap;
+        const float *fb = b.d_stats + (size_t)h->A * 6 * cap + (size_t)ant * 5 * rcap;
         const int npl = what == PB_DBG_DAG_FB ? 1 : 2;
         const int first = what == PB_DBG_POW_FB ? 0 : (what == PB_DBG_KUR_FB ? 2 : 4);
         if (nbytes != (size_t)npl * h->R * sizeof(float)) return fail(h, PB_EINVAL, "pb_debug_fetch: size");
@@ -1526,12 +1145,12 @@ extern "C" int pb_debug_fetch(pb_handle *h, int what, int ant, int seg, void *ds
     }
     if (what == PB_DBG_FLAGS) {
         if (nbytes != nb) return fail(h, PB_EINVAL, "pb_debug_fetch: size");
-        HIPCHK(h, hipMemcpy(dst, h->d_flags + (size_t)ant * cap + (size_t)seg * nb, nb, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(dst, b.d_flags + (size_t)ant * cap + (size_t)seg * nb, nb, hipMemcpyDeviceToHost));
         return PB_OK;
     }
     if (what == PB_DBG_ROWWEIGHT) {
         if (nbytes != (size_t)h->R * sizeof(float)) return fail(h, PB_EINVAL, "pb_debug_fetch: size");
-        HIPCHK(h, hipMemcpy(dst, h->d_wrow + (size_t)ant * h->S * h->R + (size_t)seg * h->R, nbytes, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(dst, b.d_wrow + (size_t)ant * h->S * h->R + (size_t)seg * h->R, nbytes, hipMemcpyDeviceToHost));
         return PB_OK;
     }
     return fail(h, PB_EINVAL, "pb_debug_fetch: unknown item");

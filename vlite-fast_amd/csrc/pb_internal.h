@@ -10,6 +10,8 @@
 
 #include "pb_hip.h"
 
+#define PB_LOCAL __attribute__((visibility("hidden")))      // shared between the library's files, not exported
+
 // D'Agostino constants (src/pb_kernels.cu:3-12 of the reference), evaluated on the host
 // with the reference's float/double mix and handed to the kernel by value.
 struct DagConsts {
@@ -58,83 +60,138 @@ struct PbSched {
 PbSched pb_read_sched();
 
 struct pb_handle {
-    pb_config cfg;
-    PbSched sched;
-    int R;                 // rows per segment
-    int S;                 // max segments
-    int A;                 // antennas
-    size_t seg_samples;    // R * 12500
-    size_t nblk_seg;       // R * 25 (per pol)
-    size_t trim;           // code bytes per segment
-    size_t ave_per_seg;    // compact floats per segment
-    hipStream_t stream;
-    bool own_stream;
-    size_t device_bytes;
+    PB_LOCAL pb_handle() = default;    // (the member initialisers make it non-trivial: keep it out of the ABI)
+    pb_config cfg = {};
+    PbSched sched = {};
+    int R = 0;                 // rows per segment
+    int S = 0;                 // max segments
+    int A = 0;                 // antennas
+    size_t seg_samples = 0;    // R * 12500
+    size_t nblk_seg = 0;       // R * 25 (per pol)
+    size_t trim = 0;           // code bytes per segment
+    size_t ave_per_seg = 0;    // compact floats per segment
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    size_t device_bytes = 0;
 
-    uint8_t *d_in;         // [A][S][2][seg_samples]
-    uint8_t *d_vdif;       // staging for one raw 1-s block
-    int32_t *d_frame_idx;  // [2][frames] frame -> slot in block, -1 = missing
-    size_t vdif_cap;
-    int32_t *h_frame_idx[8];   // page-locked frame index per buffer set (the H2D copy of it is asynchronous)
-    size_t h_idx_cap[8];
-    hipEvent_t ev_idx[8];      // that copy has completed: the host may rewrite the index
-    uint8_t *d_flags;      // [A][S*R*25]
-    float *d_wrow;         // [A][S*R] row weights, then [A][S*R] uint32 row flag masks (pb_rowmask)
-    float *d_stats;        // debug: [A][3][2][S*R*25] pow,kur,dag
-    float *d_fraw, *d_fkur;      // hipFFT path: f32 voltages, same indexing as d_in
-    float2 *d_Xraw, *d_Xkur;     // hipFFT path: [A][S][2][R][6251]
-    float *d_Praw, *d_Pkur;      // LDS path: power [A][S][2][R][4096]; coherence: complex, float2 [A][S][2][R][4096]
-    float *d_bp;           // [A][2 streams][2 pols][4096]
-    uint8_t *d_codes;      // [A][2 streams][S][trim]
-    float *d_ave;          // [A][2 streams][S][ave_per_seg]
-    float *d_coadd_target; // nant = 1: the coadd stream's plane of antenna 0 goes here instead (pb_set_coadd_target)
-    float *d_frb_delays;   // [6251]
-    uint8_t *d_hist_in;    // taps=4: [2 slots][A][2][3][12512] last three rows of the previous batch
-    int hist_rd;           // the slot the current batch reads (its history kernel fills the other)
-    uint8_t *d_hist_flags; // taps=4: [2][A][3][25] their kurtosis flags (1 = flagged / no data)
-    uint8_t *d_hist_valid; // taps=4: [2][A][3] slot holds data
-    float *d_tapE;         // taps=4: [4][25] window energy per (tap, block) + total at [100]
-    float frb_width, frb_amp;   // inject_frb parameters (rows, amplitude factor)
-    // --- pipeline slots: the d_* buffers above (except d_bp, d_vdif, tables) exist once per
-    // set; the members above always alias the SELECTED set (pb_select_set)
-    uint8_t *h_codes;      // pinned mirror of d_codes, filled asynchronously after detect
-    hipEvent_t ev_chan;    // kernels of this set done (its D2H may start)
-    hipEvent_t ev_det;     // D2H of this set done (set may be refilled / fetched)
-    hipEvent_t ev_cl;      // pb_coadd_local has read this set's fp32 planes (next detect may overwrite)
-    int processed;         // segments of the last pb_process on this set
+    uint8_t *d_vdif = nullptr;       // staging for one raw 1-s block
+    int32_t *d_frame_idx = nullptr;  // [2][frames] frame -> slot in block, -1 = missing
+    size_t vdif_cap = 0;
+    int32_t *h_frame_idx[8] = {};    // page-locked frame index per buffer set (the H2D copy of it is asynchronous)
+    size_t h_idx_cap[8] = {};
+    hipEvent_t ev_idx[8] = {};       // that copy has completed: the host may rewrite the index
+    float *d_bp = nullptr;           // [A][2 streams][2 pols][4096]
+    float *d_frb_delays = nullptr;   // [6251]
+    uint8_t *d_hist_in = nullptr;    // taps=4: [2 slots][A][2][3][12512] last three rows of the previous batch
+    int hist_rd = 0;                 // the slot the current batch reads (its history kernel fills the other)
+    uint8_t *d_hist_flags = nullptr; // taps=4: [2][A][3][25] their kurtosis flags (1 = flagged / no data)
+    uint8_t *d_hist_valid = nullptr; // taps=4: [2][A][3] slot holds data
+    float *d_tapE = nullptr;         // taps=4: [4][25] window energy per (tap, block) + total at [100]
+    float frb_width = 0.f, frb_amp = 1.f;   // inject_frb parameters (rows, amplitude factor)
+    // --- pipeline slots: these buffers and events exist once per set (cfg.nsets); everything reads the SELECTED
+    // set through set() (pb_select_set)
     struct BufSet {
-        uint8_t *d_in, *d_flags, *d_codes, *h_codes;
-        float *d_wrow, *d_stats, *d_fraw, *d_fkur, *d_Praw, *d_Pkur, *d_ave, *d_coadd_target;
-        float2 *d_Xraw, *d_Xkur;
-        hipEvent_t ev_chan, ev_det, ev_cl;
-        int processed;
+        uint8_t *d_in = nullptr;         // [A][S][2][seg_samples]
+        uint8_t *d_flags = nullptr;      // [A][S*R*25]
+        float *d_wrow = nullptr;         // [A][S*R] row weights, then [A][S*R] uint32 row flag masks (pb_rowmask)
+        float *d_stats = nullptr;        // debug: [A][3][2][S*R*25] pow,kur,dag
+        float *d_fraw = nullptr, *d_fkur = nullptr;    // hipFFT path: f32 voltages, same indexing as d_in
+        float2 *d_Xraw = nullptr, *d_Xkur = nullptr;   // hipFFT path: [A][S][2][R][6251]
+        float *d_Praw = nullptr, *d_Pkur = nullptr;    // LDS path: power [A][S][2][R][4096]; coherence: complex, float2 [A][S][2][R][4096]
+        uint8_t *d_codes = nullptr;      // [A][2 streams][S][trim]
+        uint8_t *h_codes = nullptr;      // pinned mirror of d_codes, filled asynchronously after detect
+        float *d_ave = nullptr;          // [A][2 streams][S][ave_per_seg]
+        float *d_coadd_target = nullptr; // nant = 1: the coadd stream's plane of antenna 0 goes here instead (pb_set_coadd_target)
+        hipEvent_t ev_chan = nullptr;    // kernels of this set done (its D2H may start)
+        hipEvent_t ev_det = nullptr;     // D2H of this set done (set may be refilled / fetched)
+        hipEvent_t ev_cl = nullptr;      // pb_coadd_local has read this set's fp32 planes (next detect may overwrite)
+        int processed = 0;               // segments of the last pb_process on this set
     };
-    int fuse;                                          // PB_FUSE_KURTOSIS at pb_create (pb_fused_kurtosis)
+    int fuse = 0;                                      // PB_FUSE_KURTOSIS at pb_create (pb_fused_kurtosis)
     std::vector<BufSet> sets;
-    int cur_set;
-    hipStream_t s_det;     // detect of the previous batch (pipelined mode); copy-out in the single-set mode
-    hipStream_t s_copy;    // copy-out of the filterbank bytes in pipelined mode, so that it does not hold up the next detect
-    hipStream_t s_kur;     // kurtosis of the next batch, beside detect of the previous one
-    hipEvent_t ev_fftdone, ev_kur, ev_alldone;
-    hipEvent_t ev_hist;    // taps = 4: the batch's last rows and flags have been kept for the next one
-    int last_set;          // buffer set of the previous pb_process (-1: none)
-    bool staged;           // input has been queued on s_kur since the last pb_process
-    uint8_t *d_coadd_codes, *h_coadd_codes;   // [2][S*trim] coadded bytes (device / pinned), lazily
-    hipEvent_t ev_coadd[2];
-    hipStream_t s_coadd;   // stream of pb_coadd_local / pb_coadd_finish (nullptr: the main stream)
-    int coadd_slot, coadd_last;
-    FftTables ft;
-    DagConsts dag, dag_fb;   // D'Agostino constants for N = 500 (blocks) and N = 12500 (FFT rows, K4)
-    int dag_bands;           // 1: crossings located (flags decided without the cube root); -1: PB_DAG_BANDS=0; -2: search failed, fallback
-    DagConsts *d_dag;        // dag in device memory
+    int cur_set = 0;
+    BufSet &set() { return sets[cur_set]; }
+    const BufSet &set() const { return sets[cur_set]; }
+    hipStream_t s_det = nullptr;     // detect of the previous batch (pipelined mode); copy-out in the single-set mode
+    hipStream_t s_copy = nullptr;    // copy-out of the filterbank bytes in pipelined mode, so that it does not hold up the next detect
+    hipStream_t s_kur = nullptr;     // kurtosis of the next batch, beside detect of the previous one
+    hipEvent_t ev_fftdone = nullptr, ev_kur = nullptr, ev_alldone = nullptr;
+    hipEvent_t ev_hist = nullptr;    // taps = 4: the batch's last rows and flags have been kept for the next one
+    int last_set = -1;               // buffer set of the previous pb_process (-1: none)
+    bool staged = false;             // input has been queued on s_kur since the last pb_process
+    uint8_t *d_coadd_codes = nullptr, *h_coadd_codes = nullptr;   // [2][S*trim] coadded bytes (device / pinned), lazily
+    hipEvent_t ev_coadd[2] = {};
+    hipStream_t s_coadd = nullptr;   // stream of pb_coadd_local / pb_coadd_finish (nullptr: the main stream)
+    int coadd_slot = 0, coadd_last = 0;
+    FftTables ft = {};
+    DagConsts dag = {}, dag_fb = {};   // D'Agostino constants for N = 500 (blocks) and N = 12500 (FFT rows, K4)
+    int dag_bands = 0;               // 1: crossings located (flags decided without the cube root); -1: PB_DAG_BANDS=0; -2: search failed, fallback
+    DagConsts *d_dag = nullptr;      // dag in device memory
     std::map<long, hipfftHandle> plans;
 
-    bool profile;
-    pb_timers timers;
+    bool profile = false;
+    pb_timers timers = {};
     struct Pending { int stage; hipEvent_t a, b; };
     std::vector<Pending> pending;        // recorded, not yet read back
     std::vector<hipEvent_t> ev_pool;     // free events
     std::string err;
+};
+
+// Launchers enqueue on h->stream: this sends them to another stream for one scope and puts the handle back on its own
+// stream on every way out of it.
+struct StreamScope {
+    pb_handle *h;
+    hipStream_t saved;
+    StreamScope(pb_handle *h_, hipStream_t s) : h(h_), saved(h_->stream) { h->stream = s; }
+    ~StreamScope() { h->stream = saved; }
+};
+
+// ---- what pb_api.hip and pb_coadd.hip share (defined in pb_api.hip unless inline here) ----
+#define HIPCHK(h, call)                                                                   \
+    do {                                                                                  \
+        hipError_t e_ = (call);                                                           \
+        if (e_ != hipSuccess) {                                                           \
+            (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                 \
+            return PB_EHIP;                                                               \
+        }                                                                                 \
+    } while (0)
+
+PB_LOCAL int fail(pb_handle *h, int code, const std::string &msg);   // h = nullptr: the error pb_create reports
+PB_LOCAL hipError_t sync_all(pb_handle *h);
+
+template <class T>
+static hipError_t dmalloc(pb_handle *h, T **p, size_t n)
+{
+    if (n == 0) { *p = nullptr; return hipSuccess; }
+    hipError_t e = hipMalloc((void **)p, n * sizeof(T));
+    if (e == hipSuccess) h->device_bytes += n * sizeof(T);
+    return e;
+}
+
+// Per-stage device time without disturbing the stream: each stage records a pair of events
+// from a pool; pb_get_timers synchronises once and reads them all back.
+PB_LOCAL hipEvent_t take_event(pb_handle *h);
+PB_LOCAL void retire_done(pb_handle *h);
+PB_LOCAL void drain_timers(pb_handle *h);
+struct StageTimer {
+    pb_handle *h;
+    int stage;
+    hipEvent_t a, b;
+    StageTimer(pb_handle *h_, int s) : h(h_), stage(s), a(nullptr), b(nullptr)
+    {
+        if (h->profile) {
+            if (h->ev_pool.size() < 2) retire_done(h);
+            a = take_event(h);
+            b = take_event(h);
+            (void)hipEventRecord(a, h->stream);
+        }
+    }
+    void stop()
+    {
+        if (!h->profile) return;
+        (void)hipEventRecord(b, h->stream);
+        h->pending.push_back({stage, a, b});
+    }
 };
 
 // The channeliser computes the kurtosis flags of its own rows (k_channelize_kur) instead of a kurtosis pass in
@@ -147,7 +204,7 @@ bool pb_fused_kurtosis(const pb_handle *h);
 #define PB_EXPERIMENTS 0
 #endif
 // row flag masks (bit r = kurtosis block r of the row is flagged), written by k_kurtosis_row behind the weights
-static inline uint32_t *pb_rowmask(pb_handle *h) { return (uint32_t *)(h->d_wrow + (size_t)h->A * h->S * h->R); }
+static inline uint32_t *pb_rowmask(pb_handle *h) { return (uint32_t *)(h->set().d_wrow + (size_t)h->A * h->S * h->R); }
 
 // ---- launchers (each enqueues on h->stream and returns a hipError_t) ----
 hipError_t launch_kurtosis_flag(pb_handle *h, int nseg, bool write_f32);
@@ -166,6 +223,7 @@ hipError_t launch_pfb_weights(pb_handle *h, int nseg);
 hipError_t launch_pfb_history(pb_handle *h, int nseg);   // taps = 4: the batch's last three rows and flags into the history slot the NEXT batch reads
 hipError_t launch_channelize_f32(pb_handle *h, const float *d_x, int nrows, int taps, float2 *d_out);
 hipError_t launch_coadd_local(pb_handle *h, int nseg, float *d_sum, int accumulate, hipStream_t st);
+hipError_t launch_coadd_local_codes(pb_handle *h, int nseg, float *d_sum, int accumulate, hipStream_t st);   // coadd_codes.hip
 hipError_t launch_coadd_digitise_flat(pb_handle *h, const float *d_sum, size_t nfloat, float scale, uint8_t *d_codes,
                                       hipStream_t st);
 hipError_t launch_coadd_tree(const float *const *leaves, int n, float *d_dst, size_t nfloat, hipStream_t st);
