@@ -259,6 +259,57 @@ int pb_coadd_finish(pb_handle *h, int nseg, const float *d_sum, int nant_total,
 /* pinned-host view of the coadded bytes of the latest (age 0) or previous (age 1) pb_coadd_finish */
 int pb_coadd_fetch_ptr(pb_handle *h, int age, const uint8_t **codes);
 
+/* ---- correlator: the X step over a handle's antennas (reference: analysis/baseband.py `correlate` :807 and
+ * analysis/beamforming.py :446, which form the per-channel correlation matrix of all antennas over FFT chunks; the F
+ * step is this library's own 12500-point FFT).  Needs coherence = 1: the channeliser then leaves the complex in-band
+ * spectra of every antenna, both pols and both streams on the device, and these calls pair antenna i with antenna j.
+ * Definition, operation by operation (THIS project's own; tests/correlate_ref.py restates it, tests/golden/
+ * reference_correlate.npz ties it to the reference's correlate / get_delays / fit_delays):
+ *   inputs     X[a][p][t][c]: the in-band spectra of the batch that the last pb_process put into the selected buffer
+ *              set -- antenna a, pol p (0 = VDIF thread 0), channel c = 0..4095, row t = seg * rows_per_seg + row counted
+ *              through the batch, 0 <= t < nseg * rows_per_seg.  The values the coherence detection reads, i.e. after
+ *              injection.  stream = PB_CORR_RAW or PB_CORR_KUR (the excised stream).
+ *   baselines  all pairs i <= j, autos included, row-major over the upper triangle:
+ *              bl = i * A - i * (i - 1) / 2 + (j - i), nbl = A (A + 1) / 2.
+ *   products   index 2 p + q stands for X_i^p conj(X_j^q): nprod = 4.  For i == j all four are still computed; product 2
+ *              is then the conjugate of product 1 and the imaginary parts of products 0 and 3 are +0.
+ *   one term   with A = (ax, ay) the value of antenna i and B = (bx, by) that of antenna j, every line one binary32
+ *              operation, left to right, no contraction (the lines of the coherence definition above, so product 1 of
+ *              an auto is its un-normalised CR / CI):
+ *                  re = ax*bx + ay*by          im = ay*bx - ax*by
+ *   gates      a call carries ngate gates; gate g has a first row per channel, row0[g][c], and all gates share one
+ *              length nrows.  The value for (g, bl, prod, c) starts from acc_re = acc_im = +0.0f and adds the terms of
+ *              rows row0[g][c] .. row0[g][c] + nrows - 1 IN ROW ORDER, acc = acc + term, in binary32.  A window may
+ *              cross segment boundaries; one that leaves [0, nseg * rows_per_seg) is refused (PB_EINVAL).
+ *   rows_used  int32 per (g, bl, c).  Raw stream: nrows.  Excised stream: the number of rows of the window whose row
+ *              weight (after apply_kurtosis, as pb_fetch's `weights` of npol = 2) is > 0 for both antenna i and antenna
+ *              j.  Rows of weight 0 are still added -- their spectra are zero; the definition has no skip.
+ * The sum order is fixed, so the parallelism comes from gates x channels x baseline tiles and nothing splits a gate's
+ * rows: callers keep gates at or below one segment and add gates in double on the host (correlate.py does).
+ * Outputs (host memory, either may be NULL): vis float32 [ngate][nbl][4][4096][2] (re, im); rows_used int32
+ * [ngate][nbl][4096].
+ *   pb_correlate        the gated call with ngate = nseg * rows_per_seg / int_rows and row0[g][c] = g * int_rows;
+ *                       int_rows must divide nseg * rows_per_seg and need not divide rows_per_seg.  *ngate (may be
+ *                       NULL) receives the number of gates.
+ *   pb_correlate_gated  row0 is int32 [ngate][4096] on the host.
+ *   pb_correlate_info   nbl and nprod (= 4) of the handle.
+ *   pb_correlate_timers device time of the last call in ms: the kernels; the copy to the host.
+ * Both run the same kernel on the SELECTED set (pb_select_set), on a stream of their own behind that set's channeliser
+ * and detect, and return when their outputs have arrived -- so before anything that refills the set can be queued.  The
+ * library owns and grows the device buffers and frees them in pb_destroy; pb_query's device_bytes grows by them (the
+ * visibilities, rows_used, the first rows and, on the excised stream, the row counts).  No other state of the handle
+ * changes: what pb_fetch returns afterwards is what it returns without the call.
+ * Refused, with a pb_last_error text: PB_EINVAL for coherence = 0, a stream the handle's rfi_mode does not produce,
+ * int_rows / nrows / ngate / nseg <= 0, int_rows not dividing the batch, a window out of range, nant > 8; PB_ESTATE for
+ * nseg above what the set's last pb_process processed, or no pb_process on the set yet. */
+#define PB_CORR_RAW 0
+#define PB_CORR_KUR 1
+int pb_correlate_info(const pb_handle *h, int *nbl, int *nprod);
+int pb_correlate(pb_handle *h, int stream, int nseg, int int_rows, float *vis, int32_t *rows_used, int *ngate);
+int pb_correlate_gated(pb_handle *h, int stream, int nseg, const int32_t *row0, int ngate, int nrows,
+                       float *vis, int32_t *rows_used);
+int pb_correlate_timers(const pb_handle *h, float *ms2);
+
 int pb_profile(pb_handle *h, int enable);
 int pb_get_timers(pb_handle *h, pb_timers *out, int reset);
 int pb_debug_fetch(pb_handle *h, int what, int ant, int seg, void *dst, size_t nbytes);

@@ -1,0 +1,263 @@
+"""Visibilities and delays of a set of antennas from their voltage dumps.
+
+The X step runs on the GPU (include/pb_hip.h: pb_correlate / pb_correlate_gated, over the spectra that a
+coherence = 1 handle keeps); everything in this module is host-side numpy on its small outputs:
+
+  baselines(nant)                    the (i, j) list in the library's baseline order
+  dm_row0(dm, t0_row, nrows_total)   the per-channel first rows of a dedispersed gate
+  lag_delays(vis, ...)               the reference's get_delays / get_delays_new (analysis/baseband.py:741, :723)
+  fit_delays(delays)                 the reference's fit_delays (:773) as the linear least-squares problem it is
+
+Command line (offline; the dump files are those the hosts' --replay reads):
+
+  python -m vlite-fast_amd.correlate --replay ant0.uw ant1.uw ... [--offsets n0 n1 ...] [--stream raw|kur]
+         [--int-rows N] [--seconds N] [--dm DM --t0 ROW --width ROWS [--off-gates K]] -o out.npz
+  (--rows-per-seg R --max-seg S: the handle's batch, 1024 x 10 rows = one second by default; a file's tail that does not
+  fill a batch is left out, and the gates of --dm must lie within one batch)
+
+out.npz: vis complex128 [nbl][4][4096] (all gates added in double), rows_used int64 [nbl][4096], baselines [nbl][2],
+freqs_mhz [4096], lag_cycles / lag_samples [2 pols][nant][nant] (pol products 0 and 3), fit_samples [2][nant] and
+fit_model [2][nant][nant] (fit_delays of lag_samples, the reference's sign: lag[i][j] = m_i - m_j is positive when antenna
+j is the later one), delay_samples = -fit_samples (how many samples later than antenna 0 each antenna sees the sky:
+--offsets of these values lines the antennas up), rows (rows correlated), options (JSON).  With --dm also gate_vis complex64 [2 K + 1][nbl][4][4096] (K off-gates
+before the on-gate, the on-gate, K after it, each --width rows long and dedispersed alike), gate_rows_used,
+gate_row0 [2 K + 1][4096] (rows counted from the start of the data) and gate_on = K.
+"""
+import argparse
+import collections
+import importlib
+import json
+import sys
+
+import numpy as np
+
+NFFT, NCHAN, CHANMIN, NCHANOUT = 12500, 6251, 2155, 4096
+VLITE_RATE = 128000000
+ROW_S = NFFT / float(VLITE_RATE)            # one FFT row: 97.65625 us, 10240 rows per second
+DM_CONST = 4.15e-3                          # s GHz^2 cm^3 / pc: the injection's constant (src/pb_kernels.cu:344)
+
+
+def baselines(nant):
+    """[(i, j)] for i <= j in the library's order: bl = i * nant - i * (i - 1) / 2 + (j - i)"""
+    return [(i, j) for i in range(nant) for j in range(i, nant)]
+
+
+def chan_freqs_mhz():
+    """channel c of the 4096 sits at 384 - (2155 + c) * 64 / 6251 MHz"""
+    return 384.0 - (CHANMIN + np.arange(NCHANOUT)) * 64.0 / NCHAN
+
+
+def dm_row0(dm, t0_row, nrows_total):
+    """int32 [4096]: the first row of a gate that follows a dispersed pulse arriving in channel 0 (the top of the band) at
+    row t0_row.  Delay of channel c = dm * 4.15e-3 s * (f_c^-2 - f_0^-2), f in GHz, rounded to rows of 12500 / 128e6 s.
+    The constant is the one the front end's FRB injection uses (src/pb_kernels.cu:344: 4.15e-3, not the search's
+    4.148808e-3), so that a gate made here lies on a pulse injected there.  ValueError when a first row leaves
+    [0, nrows_total)."""
+    f = chan_freqs_mhz() * 1e-3
+    delay = float(dm) * DM_CONST * (f ** -2 - f[0] ** -2)
+    rows = int(t0_row) + np.floor(delay / ROW_S + 0.5).astype(np.int64)
+    if rows.min() < 0 or rows.max() >= nrows_total:
+        raise ValueError("dm_row0: rows %d..%d leave [0, %d)" % (rows.min(), rows.max(), nrows_total))
+    return rows.astype(np.int32)
+
+
+LagDelays = collections.namedtuple("LagDelays", "cycles samples peak third")
+
+
+def lag_delays(vis, used=None, mask=None, normalize=True):
+    """The reference's crude delay estimate (get_delays; with a mask and normalize, get_delays_new).
+    vis: complex [nbl][4][nchan] in baseline order (gates already added).  For pol products 0 and 3 and every baseline
+    i < j: c = V_ij / sqrt(V_ii V_jj) (normalize), times the mask, numpy.fft.fft over the channels, the argmax of the
+    modulus, fftfreq(nchan) there.  used (rows_used [nbl][nchan]): channels without a single used row are masked;
+    mask: bool / float [nchan].
+    -> LagDelays: cycles [2][nant][nant] in cycles per channel (antisymmetric), samples = cycles * 12500 (samples at
+    128 MS/s), peak and third = the largest and third-largest modulus of each lag spectrum."""
+    vis = np.asarray(vis)
+    nbl, nchan = vis.shape[0], vis.shape[-1]
+    nant = int(round((np.sqrt(8 * nbl + 1) - 1) / 2))
+    bls = baselines(nant)
+    assert len(bls) == nbl, "vis is not [nant (nant + 1) / 2][4][nchan]"
+    index = dict((b, k) for k, b in enumerate(bls))
+    m = np.ones(nchan) if mask is None else np.asarray(mask, float)
+    freqs = np.fft.fftfreq(nchan)
+    cycles = np.zeros((2, nant, nant))
+    peak = np.zeros((2, nant, nant))
+    third = np.zeros((2, nant, nant))
+    for k, prod in enumerate((0, 3)):
+        for (i, j), bl in index.items():
+            if i == j:
+                continue
+            c = vis[bl, prod].astype(np.complex128)
+            mm = m if used is None else m * (np.asarray(used)[bl] > 0)
+            if normalize:
+                d = np.sqrt(vis[index[(i, i)], prod].real.astype(float) * vis[index[(j, j)], prod].real.astype(float))
+                c = np.where(d > 0, c / np.where(d > 0, d, 1.0), 0)
+            y = np.abs(np.fft.fft(c * mm))
+            a = int(np.argmax(y))
+            cycles[k, i, j] = freqs[a]
+            cycles[k, j, i] = -freqs[a]
+            peak[k, i, j] = peak[k, j, i] = y[a]
+            third[k, i, j] = third[k, j, i] = np.sort(y)[-3] if nchan >= 3 else 0.0
+    return LagDelays(cycles, cycles * NFFT, peak, third)
+
+
+def fit_delays(delays):
+    """Per-antenna delays, antenna 0 at 0, that minimise the residuals of delays[i][j] = m_i - m_j over the baselines
+    i < j: the reference's fit_delays as linear least squares.  -> (m [nant], model [nant][nant])"""
+    delays = np.asarray(delays, float)
+    nant = delays.shape[0]
+    iu = np.triu_indices(nant, k=1)
+    if nant == 1:
+        return np.zeros(1), np.zeros((1, 1))
+    design = np.zeros((len(iu[0]), nant - 1))
+    for r, (i, j) in enumerate(zip(*iu)):
+        if i > 0:
+            design[r, i - 1] += 1.0
+        design[r, j - 1] -= 1.0
+    sol = np.linalg.lstsq(design, delays[iu], rcond=None)[0]
+    m = np.append(0.0, sol)
+    return m, m[:, None] - m[None, :]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the tool
+
+def make_parser():
+    p = argparse.ArgumentParser(prog="correlate", description="visibilities and delays of voltage dumps")
+    p.add_argument("--replay", nargs="+", required=True, help="one dump file per antenna (antenna = position)")
+    p.add_argument("--offsets", nargs="+", type=int, default=None, help="samples to advance each antenna by (>= 0)")
+    p.add_argument("--stream", choices=("raw", "kur"), default="raw")
+    p.add_argument("--int-rows", type=int, default=1024, help="rows per gate of the ungated correlation")
+    p.add_argument("--seconds", type=int, default=0, help="stop after this many seconds (0 = all)")
+    p.add_argument("--dm", type=float, default=None)
+    p.add_argument("--t0", type=int, default=None, help="row (from the start of the data) of the pulse in channel 0")
+    p.add_argument("--width", type=int, default=None, help="rows per on / off gate")
+    p.add_argument("--off-gates", type=int, default=2, help="off gates before and after the on gate")
+    p.add_argument("--rows-per-seg", type=int, default=1024, help="FFT rows per segment of the handle (a multiple of 8)")
+    p.add_argument("--max-seg", type=int, default=10, help="segments per batch (1024 x 10 = one second)")
+    p.add_argument("--device", type=int, default=0)
+    p.add_argument("-o", "--output", required=True)
+    return p
+
+
+def parse_args(argv=None):
+    p = make_parser()
+    a = p.parse_args(argv)
+    n = len(a.replay)
+    if n > 8:
+        p.error("at most 8 antennas")
+    if a.offsets is None:
+        a.offsets = [0] * n
+    if len(a.offsets) != n or min(a.offsets) < 0:
+        p.error("--offsets: one value >= 0 per --replay file")
+    if a.int_rows <= 0 or a.seconds < 0 or a.off_gates < 0:
+        p.error("--int-rows must be positive, --seconds and --off-gates not negative")
+    if a.rows_per_seg <= 0 or a.rows_per_seg % 8 or a.max_seg <= 0:
+        p.error("--rows-per-seg must be a positive multiple of 8, --max-seg positive")
+    if (a.rows_per_seg * a.max_seg) % a.int_rows:
+        p.error("--int-rows must divide the %d rows of a batch" % (a.rows_per_seg * a.max_seg))
+    gate = (a.dm, a.t0, a.width)
+    if any(v is not None for v in gate):
+        if any(v is None for v in gate):
+            p.error("--dm, --t0 and --width go together")
+        if a.dm < 0 or a.t0 < 0 or a.width <= 0:
+            p.error("--dm and --t0 must not be negative, --width must be positive")
+    return a
+
+
+class _Antenna(object):
+    """one dump file as a stream of pol-planar samples, its first `offset` samples dropped"""
+    SEC_BYTES = 2 * 25600 * 5032
+
+    def __init__(self, path, offset):
+        dada = importlib.import_module("vlite-fast_amd.dada")
+        self._vdif = importlib.import_module("vlite-fast_amd.vdif")
+        self._ring = dada.FileRing([path])
+        if self._ring.next_header() is None:
+            raise IOError("%s: no header" % path)
+        self._buf = np.empty((2, 0), np.uint8)
+        self._drop = offset
+        self._eod = False
+
+    def take(self, n):
+        """the next n samples per pol, [2][n], or None when the file holds fewer"""
+        while self._buf.shape[1] < n and not self._eod:
+            raw = self._ring.read(self.SEC_BYTES)
+            raw = raw[:len(raw) // (2 * 5032) * (2 * 5032)]
+            if not raw:
+                self._eod = True
+                break
+            d = self._vdif.deframe_block(np.frombuffer(raw, np.uint8))
+            if self._drop:
+                k = min(self._drop, d.shape[1])
+                d = d[:, k:]
+                self._drop -= k
+            self._buf = np.concatenate([self._buf, d], axis=1)
+        if self._buf.shape[1] < n:
+            return None
+        out, self._buf = self._buf[:, :n], self._buf[:, n:]
+        return out
+
+
+def run(args):
+    lp = importlib.import_module("vlite-fast_amd.libpb")
+    nant = len(args.replay)
+    R, S = args.rows_per_seg, args.max_seg
+    stream = lp.CORR_KUR if args.stream == "kur" else lp.CORR_RAW
+    ants = [_Antenna(p, o) for p, o in zip(args.replay, args.offsets)]
+    bls = baselines(nant)
+    vis = np.zeros((len(bls), 4, NCHANOUT), np.complex128)
+    rows_used = np.zeros((len(bls), NCHANOUT), np.int64)
+    gates = None
+    if args.dm is not None:
+        K = args.off_gates
+        starts = [args.t0 + (m - K) * args.width for m in range(2 * K + 1)]
+        batch = args.t0 // (S * R)
+        try:
+            row0 = np.stack([dm_row0(args.dm, s - batch * S * R, S * R - args.width + 1) for s in starts])
+        except ValueError as e:
+            raise SystemExit("correlate: the gates must lie within one batch of %d rows (%s)" % (S * R, e))
+        gates = dict(batch=batch, row0=row0)
+    nsec = 0                                     # batches done
+    max_batches = -(-args.seconds * 10240 // (S * R)) if args.seconds else 0
+    with lp.PbHandle(device=args.device, nant=nant, nbit=8, npol=2, rfi_mode=2 if stream else 0, rows_per_seg=R,
+                     max_seg=S, coherence=True) as h:
+        while not max_batches or nsec < max_batches:
+            blocks = [a.take(S * R * NFFT) for a in ants]
+            if any(b is None for b in blocks):
+                break
+            for k, b in enumerate(blocks):
+                for s in range(S):
+                    h.submit_planar(k, s, b[0, s * R * NFFT:(s + 1) * R * NFFT], b[1, s * R * NFFT:(s + 1) * R * NFFT])
+            h.process(S)
+            v, u = h.correlate(stream, S, args.int_rows)
+            vis += v.astype(np.complex128).sum(axis=0)
+            rows_used += u.astype(np.int64).sum(axis=0)
+            if gates is not None and gates["batch"] == nsec:
+                gates["vis"], gates["used"] = h.correlate_gated(stream, S, gates["row0"], args.width)
+            nsec += 1
+    if nsec == 0:
+        raise SystemExit("correlate: the files hold less than one batch of %d rows" % (S * R))
+    if gates is not None and "vis" not in gates:
+        raise SystemExit("correlate: --t0 lies beyond the %d batches read" % nsec)
+    lag = lag_delays(vis, used=rows_used)
+    fits = [fit_delays(lag.samples[k]) for k in range(2)]
+    out = dict(vis=vis, rows_used=rows_used, baselines=np.array(bls, np.int32), freqs_mhz=chan_freqs_mhz(),
+               lag_cycles=lag.cycles, lag_samples=lag.samples, lag_peak=lag.peak, lag_third=lag.third,
+               fit_samples=np.stack([f[0] for f in fits]), fit_model=np.stack([f[1] for f in fits]),
+               delay_samples=-np.stack([f[0] for f in fits]),
+               rows=np.int64(nsec * S * R), options=np.array(json.dumps(vars(args), sort_keys=True)))
+    if gates is not None:
+        out.update(gate_vis=gates["vis"], gate_rows_used=gates["used"],
+                   gate_row0=gates["row0"].astype(np.int64) + gates["batch"] * S * R, gate_on=np.int64(args.off_gates))
+    np.savez(args.output, **out)
+    return out
+
+
+def main(argv=None):
+    run(parse_args(argv))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

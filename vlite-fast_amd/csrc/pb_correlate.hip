@@ -1,0 +1,346 @@
+// The correlator's X step (include/pb_hip.h: pb_correlate*): every antenna pair of a handle's batch, per channel, from
+// the complex in-band spectra that the coherence channeliser leaves in HBM (BufSet::d_Praw / d_Pkur, float2
+// [A][S][2][R][4096]).  The sum over a gate's rows is in row order, so a lane walks its channel's window alone and the
+// parallelism is gates x channels x antenna tiles.
+//
+// k_correlate: one 64-lane workgroup = 64 channels of one gate and one antenna tile; a lane owns one channel and keeps
+//   the tile's accumulators (8 floats per baseline) in registers.  Every spectrum value of the tile is loaded once and
+//   serves all of the tile's baselines and products; the loads of the next U rows are in flight while the current U
+//   rows are added.  A gate's window differs per channel only in its first row: the addresses are coalesced over the
+//   channels whenever neighbouring row0 are equal and correct when they are not.  No LDS, no atomics.
+//   Tiles: antennas in groups of four; a group against itself (k_correlate<N, N, true>: N (N + 1) / 2 baselines, 80
+//   accumulators at N = 4) and, beyond four antennas, group 0 against two antennas of group 1 at a time
+//   (k_correlate<4, N, false>: 4 N baselines).
+// k_corr_prefix: per baseline the running count of rows whose weight is > 0 for both antennas (one wave, ballots), so
+//   that rows_used of the excised stream is a difference of two entries.
+#include "pb_internal.h"
+
+#define CORR_MAX_ANT 8
+
+struct CorrArgs {
+    const float2 *X;       // one stream's spectra [A][S][2][R][4096]
+    const int32_t *row0;   // [ngate][4096] first row of the gate per channel
+    const int32_t *pref;   // [nbl][T + 1] rows before t with both weights > 0; nullptr on the raw stream
+    float2 *vis;           // [ngate][nbl][4][4096]
+    int32_t *used;         // [ngate][nbl][4096]
+    int A, S, R, T, nrows;
+    int i0, j0;            // first antenna of the tile's rows and columns
+};
+
+struct pb_corr_state {
+    hipStream_t st = nullptr;
+    hipEvent_t ev[3] = {};
+    float *d_vis = nullptr;
+    int32_t *d_used = nullptr, *d_row0 = nullptr, *d_pref = nullptr;
+    size_t vis_cap = 0, used_cap = 0, row0_cap = 0, pref_cap = 0;      // elements
+    std::vector<int32_t> h_row0;
+    float ms[2] = {0.f, 0.f};
+};
+
+namespace {
+
+__host__ __device__ inline int corr_bl(int A, int i, int j) { return i * A - i * (i - 1) / 2 + (j - i); }
+
+// rows in flight per buffer: about 32 8-byte loads per lane and buffer
+constexpr int corr_rows_in_flight(int nl) { return nl == 1 ? 16 : nl == 2 ? 8 : nl == 3 ? 5 : nl == 4 ? 4 : 2; }
+
+}  // namespace
+
+template <int NI, int NJ, bool DIAG>
+__global__ __launch_bounds__(64) void k_correlate(CorrArgs a)
+{
+    constexpr int NL = DIAG ? NI : NI + NJ;              // antennas the tile reads
+    constexpr int NBL = DIAG ? NI * (NI + 1) / 2 : NI * NJ;
+    constexpr int U = corr_rows_in_flight(NL);
+    const int c = blockIdx.x * 64 + threadIdx.x, g = blockIdx.y;
+    const int R = a.R, nrows = a.nrows;
+    const size_t pol_stride = (size_t)R * PB_NCHANOUT, seg_stride = 2 * pol_stride, ant_stride = (size_t)a.S * seg_stride;
+    const int r0 = a.row0[(size_t)g * PB_NCHANOUT + c];
+
+    const float2 *xp[NL];
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+        const int ant = (DIAG || l < NI) ? a.i0 + l : a.j0 + (l - NI);
+        xp[l] = a.X + (size_t)ant * ant_stride + c;
+    }
+    // the loader's position: row k of the window, as (row within its segment, offset of that row in an antenna's plane)
+    int kload = 0, row = r0 % R;
+    size_t off = (size_t)(r0 / R) * seg_stride + (size_t)row * PB_NCHANOUT;
+
+    float2 cur[U][NL][2], nxt[U][NL][2];
+    auto request = [&]() {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+            for (int l = 0; l < NL; ++l) {
+                nxt[u][l][0] = xp[l][off];
+                nxt[u][l][1] = xp[l][off + pol_stride];
+            }
+            // rows past the window's end repeat its last row (loaded, never added): no address leaves the window
+            if (kload < nrows - 1) {
+                ++kload;
+                ++row;
+                off += PB_NCHANOUT;
+                if (row == R) {
+                    row = 0;
+                    off += seg_stride - pol_stride;
+                }
+            }
+        }
+    };
+
+    float2 acc[NBL][4];
+#pragma unroll
+    for (int b = 0; b < NBL; ++b)
+#pragma unroll
+        for (int pr = 0; pr < 4; ++pr) acc[b][pr] = make_float2(0.f, 0.f);
+
+    request();
+    for (int kb = 0; kb < nrows; kb += U) {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int l = 0; l < NL; ++l) {
+                cur[u][l][0] = nxt[u][l][0];
+                cur[u][l][1] = nxt[u][l][1];
+            }
+        if (kb + U < nrows) request();
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (kb + u < nrows) {
+                int b = 0;
+#pragma unroll
+                for (int i = 0; i < NI; ++i)
+#pragma unroll
+                    for (int j = DIAG ? i : 0; j < (DIAG ? NI : NJ); ++j) {
+                        const int lj = DIAG ? j : NI + j;
+#pragma unroll
+                        for (int p = 0; p < 2; ++p)
+#pragma unroll
+                            for (int q = 0; q < 2; ++q) {
+                                // one term (include/pb_hip.h): the lines of the coherence definition
+                                const float ax = cur[u][i][p].x, ay = cur[u][i][p].y;
+                                const float bx = cur[u][lj][q].x, by = cur[u][lj][q].y;
+                                const float rxx = ax * bx, ryy = ay * by;
+                                const float re = rxx + ryy;
+                                const float iyx = ay * bx, ixy = ax * by;
+                                const float im = iyx - ixy;
+                                acc[b][2 * p + q].x = acc[b][2 * p + q].x + re;
+                                acc[b][2 * p + q].y = acc[b][2 * p + q].y + im;
+                            }
+                        ++b;
+                    }
+            }
+        }
+    }
+
+    const int nbl = a.A * (a.A + 1) / 2;
+    int b = 0;
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = DIAG ? i : 0; j < (DIAG ? NI : NJ); ++j) {
+            const int bl = corr_bl(a.A, a.i0 + i, DIAG ? a.i0 + j : a.j0 + j);
+            const size_t o = (size_t)g * nbl + bl;
+            if (a.vis) {
+#pragma unroll
+                for (int pr = 0; pr < 4; ++pr) a.vis[(o * 4 + pr) * PB_NCHANOUT + c] = acc[b][pr];
+            }
+            if (a.used) {
+                int n = nrows;
+                if (a.pref) {
+                    const int32_t *P = a.pref + (size_t)bl * (a.T + 1);
+                    n = P[r0 + nrows] - P[r0];
+                }
+                a.used[o * PB_NCHANOUT + c] = n;
+            }
+            ++b;
+        }
+}
+
+// pref[bl][t] = the number of rows before t whose weight is > 0 for antenna i and for antenna j, t = 0 .. T
+__global__ __launch_bounds__(64) void k_corr_prefix(const float *wrow, int A, size_t ant_stride, int T, int32_t *pref)
+{
+    const int i = blockIdx.x, j = blockIdx.y;
+    if (j < i) return;
+    const float *wi = wrow + (size_t)i * ant_stride, *wj = wrow + (size_t)j * ant_stride;
+    int32_t *P = pref + (size_t)corr_bl(A, i, j) * (T + 1);
+    const int lane = threadIdx.x;
+    int total = 0;
+    if (lane == 0) P[0] = 0;
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        const int t = t0 + lane;
+        const bool ok = t < T && wi[t] > 0.f && wj[t] > 0.f;
+        const unsigned long long m = __ballot(ok);
+        if (t < T) P[t + 1] = total + __popcll(m & (~0ull >> (63 - lane)));
+        total += __popcll(m);
+    }
+}
+
+template <int NI, int NJ, bool DIAG> static void corr_launch(const CorrArgs &a, int ngate, hipStream_t st)
+{
+    k_correlate<NI, NJ, DIAG><<<dim3(PB_NCHANOUT / 64, ngate), 64, 0, st>>>(a);
+}
+
+static void corr_launch_all(CorrArgs a, int ngate, hipStream_t st)
+{
+    for (int i0 = 0; i0 < a.A; i0 += 4) {
+        a.i0 = a.j0 = i0;
+        switch (a.A - i0 < 4 ? a.A - i0 : 4) {
+        case 1: corr_launch<1, 1, true>(a, ngate, st); break;
+        case 2: corr_launch<2, 2, true>(a, ngate, st); break;
+        case 3: corr_launch<3, 3, true>(a, ngate, st); break;
+        default: corr_launch<4, 4, true>(a, ngate, st); break;
+        }
+    }
+    a.i0 = 0;
+    for (int j0 = 4; j0 < a.A; j0 += 2) {
+        a.j0 = j0;
+        if (a.A - j0 >= 2) corr_launch<4, 2, false>(a, ngate, st);
+        else corr_launch<4, 1, false>(a, ngate, st);
+    }
+}
+
+template <class T> static hipError_t corr_grow(pb_handle *h, T **p, size_t *cap, size_t n)
+{
+    if (n <= *cap) return hipSuccess;
+    if (*p) {
+        (void)hipFree(*p);
+        h->device_bytes -= *cap * sizeof(T);
+        *p = nullptr;
+        *cap = 0;
+    }
+    hipError_t e = dmalloc(h, p, n);
+    if (e == hipSuccess) *cap = n;
+    return e;
+}
+
+void pb_correlate_free(pb_handle *h)
+{
+    pb_corr_state *cs = h->corr;
+    if (!cs) return;
+    if (cs->st) { (void)hipStreamSynchronize(cs->st); (void)hipStreamDestroy(cs->st); }
+    for (hipEvent_t e : cs->ev)
+        if (e) (void)hipEventDestroy(e);
+    void *ptrs[] = {cs->d_vis, cs->d_used, cs->d_row0, cs->d_pref};
+    for (void *p : ptrs)
+        if (p) (void)hipFree(p);
+    delete cs;
+    h->corr = nullptr;
+}
+
+// what both entry points refuse before they look at the gates
+static int corr_check(pb_handle *h, const char *what, int stream, int nseg)
+{
+    const std::string w(what);
+    if (!h->cfg.coherence) return fail(h, PB_EINVAL, w + ": the handle keeps no spectra (needs coherence = 1)");
+    if (h->A > CORR_MAX_ANT) return fail(h, PB_EINVAL, w + ": at most 8 antennas");
+    if (stream != PB_CORR_RAW && stream != PB_CORR_KUR) return fail(h, PB_EINVAL, w + ": stream must be 0 (raw) or 1 (excised)");
+    if ((stream == PB_CORR_RAW && h->cfg.rfi_mode == 1) || (stream == PB_CORR_KUR && h->cfg.rfi_mode == 0))
+        return fail(h, PB_EINVAL, w + ": the handle's rfi_mode does not produce that stream");
+    if (nseg < 1) return fail(h, PB_EINVAL, w + ": nseg must be positive");
+    const pb_handle::BufSet &b = h->set();
+    if (b.processed < 1) return fail(h, PB_ESTATE, w + ": no pb_process on the selected set yet");
+    if (nseg > b.processed) return fail(h, PB_ESTATE, w + ": more segments than the set's last pb_process processed");
+    return PB_OK;
+}
+
+// row0 is in h->corr->h_row0, checked: upload, launch, copy out, wait
+static int corr_run(pb_handle *h, int stream, int nseg, int ngate, int nrows, float *vis, int32_t *rows_used)
+{
+    pb_corr_state *cs = h->corr;
+    const int nbl = h->A * (h->A + 1) / 2, T = nseg * h->R;
+    const size_t nused = (size_t)ngate * nbl * PB_NCHANOUT, nvis = nused * 8;
+    if (nvis * sizeof(float) > ((size_t)2 << 30)) return fail(h, PB_EINVAL, "pb_correlate: outputs beyond 2 GiB; use fewer gates per call");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!cs->st) {
+        HIPCHK(h, hipStreamCreateWithFlags(&cs->st, hipStreamNonBlocking));
+        for (hipEvent_t &e : cs->ev) HIPCHK(h, hipEventCreate(&e));
+    }
+    if (vis) HIPCHK(h, corr_grow(h, &cs->d_vis, &cs->vis_cap, nvis));
+    if (rows_used) HIPCHK(h, corr_grow(h, &cs->d_used, &cs->used_cap, nused));
+    HIPCHK(h, corr_grow(h, &cs->d_row0, &cs->row0_cap, (size_t)ngate * PB_NCHANOUT));
+    const bool kur = stream == PB_CORR_KUR;
+    if (kur && rows_used) HIPCHK(h, corr_grow(h, &cs->d_pref, &cs->pref_cap, (size_t)nbl * (T + 1)));
+
+    const pb_handle::BufSet &b = h->set();
+    // behind the set's channeliser and detect (ev_chan); whatever refills the set is queued by a later call, and this
+    // one returns only when its own stream has drained
+    HIPCHK(h, hipStreamWaitEvent(cs->st, b.ev_chan, 0));
+    HIPCHK(h, hipMemcpyAsync(cs->d_row0, cs->h_row0.data(), (size_t)ngate * PB_NCHANOUT * sizeof(int32_t),
+                             hipMemcpyHostToDevice, cs->st));
+    HIPCHK(h, hipEventRecord(cs->ev[0], cs->st));
+    CorrArgs a;
+    a.X = (const float2 *)(kur ? b.d_Pkur : b.d_Praw);
+    a.row0 = cs->d_row0;
+    a.pref = nullptr;
+    a.vis = vis ? (float2 *)cs->d_vis : nullptr;
+    a.used = rows_used ? cs->d_used : nullptr;
+    a.A = h->A;
+    a.S = h->S;
+    a.R = h->R;
+    a.T = T;
+    a.nrows = nrows;
+    a.i0 = a.j0 = 0;
+    if (kur && rows_used) {
+        k_corr_prefix<<<dim3(h->A, h->A), 64, 0, cs->st>>>(b.d_wrow, h->A, (size_t)h->S * h->R, T, cs->d_pref);
+        a.pref = cs->d_pref;
+    }
+    corr_launch_all(a, ngate, cs->st);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(cs->ev[1], cs->st));
+    if (vis) HIPCHK(h, hipMemcpyAsync(vis, cs->d_vis, nvis * sizeof(float), hipMemcpyDeviceToHost, cs->st));
+    if (rows_used) HIPCHK(h, hipMemcpyAsync(rows_used, cs->d_used, nused * sizeof(int32_t), hipMemcpyDeviceToHost, cs->st));
+    HIPCHK(h, hipEventRecord(cs->ev[2], cs->st));
+    HIPCHK(h, hipStreamSynchronize(cs->st));
+    HIPCHK(h, hipEventElapsedTime(&cs->ms[0], cs->ev[0], cs->ev[1]));
+    HIPCHK(h, hipEventElapsedTime(&cs->ms[1], cs->ev[1], cs->ev[2]));
+    return PB_OK;
+}
+
+extern "C" int pb_correlate_info(const pb_handle *h, int *nbl, int *nprod)
+{
+    if (!h) return PB_EINVAL;
+    if (nbl) *nbl = h->A * (h->A + 1) / 2;
+    if (nprod) *nprod = 4;
+    return PB_OK;
+}
+
+extern "C" int pb_correlate_gated(pb_handle *h, int stream, int nseg, const int32_t *row0, int ngate, int nrows,
+                                  float *vis, int32_t *rows_used)
+{
+    if (!h) return PB_EINVAL;
+    if (int rc = corr_check(h, "pb_correlate_gated", stream, nseg)) return rc;
+    if (ngate <= 0 || nrows <= 0) return fail(h, PB_EINVAL, "pb_correlate_gated: ngate and nrows must be positive");
+    if (!row0) return fail(h, PB_EINVAL, "pb_correlate_gated: row0 is null");
+    const int T = nseg * h->R;
+    const size_t n = (size_t)ngate * PB_NCHANOUT;
+    for (size_t k = 0; k < n; ++k)
+        if (row0[k] < 0 || row0[k] > T - nrows) return fail(h, PB_EINVAL, "pb_correlate_gated: a window leaves the batch's rows");
+    if (!h->corr) h->corr = new pb_corr_state;
+    h->corr->h_row0.assign(row0, row0 + n);
+    return corr_run(h, stream, nseg, ngate, nrows, vis, rows_used);
+}
+
+extern "C" int pb_correlate(pb_handle *h, int stream, int nseg, int int_rows, float *vis, int32_t *rows_used, int *ngate)
+{
+    if (!h) return PB_EINVAL;
+    if (int rc = corr_check(h, "pb_correlate", stream, nseg)) return rc;
+    const int T = nseg * h->R;
+    if (int_rows <= 0 || T % int_rows) return fail(h, PB_EINVAL, "pb_correlate: int_rows must be positive and divide the batch's rows");
+    const int ng = T / int_rows;
+    if (!h->corr) h->corr = new pb_corr_state;
+    h->corr->h_row0.resize((size_t)ng * PB_NCHANOUT);
+    for (int g = 0; g < ng; ++g)
+        for (int c = 0; c < PB_NCHANOUT; ++c) h->corr->h_row0[(size_t)g * PB_NCHANOUT + c] = g * int_rows;
+    if (ngate) *ngate = ng;
+    return corr_run(h, stream, nseg, ng, int_rows, vis, rows_used);
+}
+
+extern "C" int pb_correlate_timers(const pb_handle *h, float *ms2)
+{
+    if (!h || !ms2) return PB_EINVAL;
+    ms2[0] = h->corr ? h->corr->ms[0] : 0.f;
+    ms2[1] = h->corr ? h->corr->ms[1] : 0.f;
+    return PB_OK;
+}

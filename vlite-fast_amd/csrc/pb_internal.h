@@ -123,6 +123,7 @@ struct pb_handle {
     hipEvent_t ev_coadd[2] = {};
     hipStream_t s_coadd = nullptr;   // stream of pb_coadd_local / pb_coadd_finish (nullptr: the main stream)
     int coadd_slot = 0, coadd_last = 0;
+    struct pb_corr_state *corr = nullptr;   // the correlator's stream, events and output buffers (pb_correlate.hip), lazily
     FftTables ft = {};
     DagConsts dag = {}, dag_fb = {};   // D'Agostino constants for N = 500 (blocks) and N = 12500 (FFT rows, K4)
     int dag_bands = 0;               // 1: crossings located (flags decided without the cube root); -1: PB_DAG_BANDS=0; -2: search failed, fallback
@@ -158,6 +159,7 @@ struct StreamScope {
 
 PB_LOCAL int fail(pb_handle *h, int code, const std::string &msg);   // h = nullptr: the error pb_create reports
 PB_LOCAL hipError_t sync_all(pb_handle *h);
+PB_LOCAL void pb_correlate_free(pb_handle *h);                       // pb_correlate.hip: what pb_destroy releases
 
 template <class T>
 static hipError_t dmalloc(pb_handle *h, T **p, size_t n)

@@ -62,7 +62,8 @@ EXPORTS = ["pb_config_default", "pb_create", "pb_destroy", "pb_last_error", "pb_
            "pb_search_gulp_run", "pb_search_gulp_advance", "pb_search_gulp_fetch", "pb_search_gulp_timers", "pb_search_set_pol",
            "pb_search_pol", "pb_search_pol_cutouts", "pb_search_pol_fetch", "pb_search_pol_timers", "pb_search_set_subbands",
            "pb_search_subbands", "pb_search_subband_dm", "pb_search_subband_timers", "pb_search_set_rfi_chan",
-           "pb_search_rfi_chan_info"]
+           "pb_search_rfi_chan_info", "pb_correlate_info", "pb_correlate", "pb_correlate_gated", "pb_correlate_timers"]
+CORR_RAW, CORR_KUR = 0, 1
 
 _lib = None
 
@@ -182,6 +183,10 @@ def load():
     L.pb_search_subband_timers.argtypes = [vp, fp]
     L.pb_search_set_rfi_chan.argtypes = [vp, C.c_int, C.c_float]
     L.pb_search_rfi_chan_info.argtypes = [vp, ip, u8p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), i32p, i32p, u8p, fp]
+    L.pb_correlate_info.argtypes = [vp, ip, ip]
+    L.pb_correlate.argtypes = [vp, C.c_int, C.c_int, C.c_int, fp, i32p, ip]
+    L.pb_correlate_gated.argtypes = [vp, C.c_int, C.c_int, i32p, C.c_int, C.c_int, fp, i32p]
+    L.pb_correlate_timers.argtypes = [vp, fp]
     for n in EXPORTS:
         f = getattr(L, n)
         if f.restype is C.c_int or n in ("pb_create", "pb_query", "pb_sync"):
@@ -394,6 +399,47 @@ class PbHandle(object):
         p = C.POINTER(C.c_uint8)()
         self._chk(self._L.pb_coadd_fetch_ptr(self._h, age, C.byref(p)))
         return np.ctypeslib.as_array(p, shape=(nseg * self.trim,))
+
+    # ---- correlator (include/pb_hip.h: pb_correlate*; needs coherence=True)
+    def correlate_info(self):
+        """(nbl, nprod) = (nant (nant + 1) / 2, 4)"""
+        nbl, nprod = C.c_int(), C.c_int()
+        self._chk(self._L.pb_correlate_info(self._h, C.byref(nbl), C.byref(nprod)))
+        return nbl.value, nprod.value
+
+    def correlate(self, stream, nseg, int_rows):
+        """The selected set's batch in gates of int_rows rows -> (vis complex64 [ngate][nbl][4][4096],
+        rows_used int32 [ngate][nbl][4096])"""
+        nbl, nprod = self.correlate_info()
+        ngate = max(1, nseg * self.rows // int_rows) if int_rows > 0 else 1
+        vis = np.empty((ngate, nbl, nprod, NCHANOUT), np.complex64)
+        used = np.empty((ngate, nbl, NCHANOUT), np.int32)
+        ng = C.c_int()
+        self._chk(self._L.pb_correlate(self._h, stream, nseg, int_rows, vis.ctypes.data_as(C.POINTER(C.c_float)),
+                                       used.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ng)))
+        assert ng.value == ngate
+        return vis, used
+
+    def correlate_gated(self, stream, nseg, row0, nrows):
+        """row0: int32 [ngate][4096], the first row of each gate per channel; every gate is nrows long.
+        -> (vis, rows_used) as correlate()"""
+        row0 = np.ascontiguousarray(row0, np.int32)
+        if row0.ndim != 2 or row0.shape[1] != NCHANOUT:
+            raise ValueError("row0 must be [ngate][%d]" % NCHANOUT)
+        ngate = row0.shape[0]
+        nbl, nprod = self.correlate_info()
+        vis = np.empty((ngate, nbl, nprod, NCHANOUT), np.complex64)
+        used = np.empty((ngate, nbl, NCHANOUT), np.int32)
+        self._chk(self._L.pb_correlate_gated(self._h, stream, nseg, row0.ctypes.data_as(C.POINTER(C.c_int32)), ngate,
+                                             nrows, vis.ctypes.data_as(C.POINTER(C.c_float)),
+                                             used.ctypes.data_as(C.POINTER(C.c_int32))))
+        return vis, used
+
+    def correlate_timers(self):
+        """device ms of the last correlate call: (kernels, copy to the host)"""
+        ms = np.zeros(2, np.float32)
+        self._chk(self._L.pb_correlate_timers(self._h, _f32(ms)))
+        return float(ms[0]), float(ms[1])
 
     def profile(self, enable=True):
         self._chk(self._L.pb_profile(self._h, int(enable)))
