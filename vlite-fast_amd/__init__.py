@@ -12,7 +12,11 @@ Only the hot path of the reference's process_baseband executable lives here:
   process_baseband.py   the executable's host side, same command-line flags
   genbase.py       genbase-style synthetic baseband (test-side producer)
   coadd.py         incoherent antenna sum across GPUs (torch.distributed / RCCL)
-  search.py        dedispersion + boxcar search on the filterbank (stands where heimdall stands)
+  search.py        dedispersion + boxcar search on the filterbank (stands where heimdall stands): the entry and the
+                   public name; its command line, file writers, open_search and main
+  searcher.py      Searcher, the ctypes surface of pb_search_*
+  gulp.py          GulpSearch, the search over a stream in gulps
+  candidates.py    the host's grouping of points into candidates, the candidate line, the TCP leg to the coincidencer
   triggers.py      trigger_t wire format towards the voltage dumper
 """
 __version__ = "0.1"

@@ -1,4 +1,5 @@
-"""Candidates to the coincidencer: the TCP leg heimdall's `-coincidencer host:port` plays in the reference
+"""Candidates on the host: the search's points, giants and sub-band points grouped into candidates (overlap .. subband_list,
+below the TCP leg), and candidates to the coincidencer: the TCP leg heimdall's `-coincidencer host:port` plays in the reference
 (scripts/start_heimdall_single_antenna:21 `-coincidencer vlite-nrl:27555`; server side
 /root/reference/src/trigger.py:7-8,37-43,84-123).
 
@@ -13,6 +14,8 @@ heimdall itself (third party, absent) defines what x, y and line 1 hold; the coi
 so they are written as the gulp's first sample and sample count and a column legend.
 """
 import socket
+
+import numpy as np
 
 HEIMDALL_PORT = 27555          # src/trigger.py:8
 
@@ -48,3 +51,107 @@ def parse_coincidencer(spec):
     if not host:
         return spec, HEIMDALL_PORT
     return host, int(port)
+
+
+def overlap(c, o, delta_dm=0.1, delta_w=3):
+    """The reference coincidencer's test for "the same event" between two candidates, src/candidate.py:49-65:
+    DMs within delta_dm (fractional, relative to the other's DM), widths (i1 - i0) within a factor delta_w, and the
+    sample ranges [i0, i1) overlapping.  c, o: dicts with dm, i0, i1.  delta_w None: no width test."""
+    if o["dm"] == 0 or abs(c["dm"] / o["dm"] - 1) > delta_dm:
+        if not (o["dm"] == 0 and c["dm"] == 0):
+            return False
+    if delta_w is not None:
+        w1, w2 = float(c["i1"] - c["i0"]), float(o["i1"] - o["i0"])
+        if min(w1, w2) <= 0 or max(w1, w2) / min(w1, w2) > delta_w:
+            return False
+    if c["i0"] < o["i0"]:
+        return o["i0"] < c["i1"]
+    return c["i0"] < o["i1"]
+
+
+def group_points(idm, it, sn, w, dms, tsamp, dm_tol=0.1, delta_w=None, sample0=0):
+    """Above-threshold (DM index, sample, S/N, boxcar width) points of ONE beam's search -> candidates: strongest
+    first, a candidate absorbs every point that overlaps it in time and lies within dm_tol (fractional) of its DM.
+    This clustering is this framework's own (heimdall's, which the reference runs at this place, is third-party and
+    absent: unpinned).  It uses the time and DM tests of the reference's cross-beam coincidencer (src/candidate.py:
+    53-54, 64-66) but by default NOT its width-ratio test (:57-63, delta_w = 3): the points of one series are boxcar
+    trials of the same samples, a pulse shows up at every width from 1 to 64, and splitting them by width would
+    report one pulse several times.  delta_w (e.g. 3) applies that test as well, for like-for-like experiments.
+    Ties in S/N are broken by (DM index, sample, width): the GPU appends points in arrival order, which differs from run
+    to run, and the grouping depends on the order.  Returns dicts with heimdall's nine columns."""
+    idm, it, w = np.asarray(idm, np.int64), np.asarray(it, np.int64), np.asarray(w, np.int64)
+    sn = np.asarray(sn)
+    if idm.size == 0:
+        return []
+    order = np.lexsort((w, it, idm, -sn.astype(np.float64)))
+    idm, it, sn, w = idm[order], it[order], sn[order], w[order]
+    pdm = np.asarray(dms)[idm]
+    taken = np.zeros(idm.size, bool)
+    cands = []
+    for k in range(idm.size):
+        if taken[k]:
+            continue
+        i0, i1, dm = it[k], it[k] + w[k], pdm[k]
+        near = (~taken) & (it < i1) & (it + w > i0) & (np.abs(pdm - dm) <= dm_tol * max(dm, 1.0) + 1e-9)
+        if delta_w is not None:
+            near &= (np.maximum(w, w[k]) <= delta_w * np.minimum(w, w[k]))
+        taken |= near
+        cands.append(dict(snr=float(sn[k]), peak_idx=int(sample0 + it[k]), peak_time=float((sample0 + it[k]) * tsamp),
+                          tfilt=int(np.log2(w[k])), dmi=int(idm[k]), dm=float(dm), ngiant=int(near.sum()),
+                          i0=int(sample0 + it[near].min()), i1=int(sample0 + (it[near] + w[near]).max())))
+    return cands
+
+
+def find_candidates(snr, width_log2, dms, tsamp, threshold=6.0, dm_tol=0.1, sample0=0, delta_w=None):
+    """group_points on full S/N planes (Searcher.run): every (DM, sample) at or above the threshold"""
+    idm, it = np.nonzero(snr >= threshold)
+    return group_points(idm, it, snr[idm, it], 1 << width_log2[idm, it].astype(np.int64), dms, tsamp, dm_tol, delta_w, sample0)
+
+
+def candidates_from_peaks(pk, dms, tsamp, dm_tol=0.1, sample0=0, delta_w=None):
+    """group_points on a peak list (Searcher.peaks) instead of full S/N planes"""
+    return group_points(pk["dmi"], pk["t"], pk["snr"], 1 << pk["width_log2"].astype(np.int64), dms, tsamp, dm_tol, delta_w, sample0)
+
+
+def candidates_from_giants(res, dms, tsamp, sample0=0):
+    """Searcher.giants' clusters as candidates: the dicts of group_points (ngiant = the cluster's giants) plus npoints,
+    strongest first, ties broken by (DM index, peak).  The clustering is the device's (include/pb_hip.h,
+    pb_search_set_giants), connected components of linked giants: exact and independent of any arrival order."""
+    if len(res["snr"]) == 0:
+        return []
+    sn = np.asarray(res["snr"], np.float32)
+    order = np.lexsort((res["peak"], res["dmi"], -sn.astype(np.float64)))
+    dms = np.asarray(dms)
+    return [dict(snr=float(sn[k]), peak_idx=int(sample0 + res["peak"][k]), peak_time=float((sample0 + res["peak"][k]) * tsamp),
+                 tfilt=int(res["tfilt"][k]), dmi=int(res["dmi"][k]), dm=float(dms[res["dmi"][k]]),
+                 ngiant=int(res["members"][k]), i0=int(sample0 + res["i0"][k]), i1=int(sample0 + res["i1"][k]),
+                 npoints=int(res["npoints"][k])) for k in order]
+
+
+def subband_list(nsb):
+    """the default band list of the sub-band search (include/pb_hip.h, pb_search_set_subbands, rule 2): runs (first, count)
+    of the nsb base sub-bands, staggered dyadic, widest first -- for c = nsb/2, nsb/4, .. 1 the bands (k max(c/2, 1), c),
+    k = 0, 1, .. while they fit: 2, 7, 18, 41 bands for nsb 2, 4, 8, 16"""
+    if nsb not in (2, 4, 8, 16):
+        raise ValueError("subband_list: nsb must be 2, 4, 8 or 16")
+    out, c = [], nsb // 2
+    while c >= 1:
+        step = max(c // 2, 1)
+        out += [(k * step, c) for k in range((nsb - c) // step + 1)]
+        c //= 2
+    return out
+
+
+def candidates_from_subbands(res, dms, tsamp, bands, nsb, fch1, foff, nchan, sample0=0):
+    """Searcher.subbands' points as candidates: one group_points call over all of them, whatever their band; each dict also
+    gets band = (first, count) and snr_full of the point at the candidate's (dmi, peak) -- there is one point per cell --
+    and f_lo, f_hi in MHz, the outer edges of the band's channels [first nchan/nsb, (first + count) nchan/nsb)."""
+    cands = group_points(res["dmi"], res["t"], res["snr"], 1 << np.asarray(res["width_log2"], np.int64), dms, tsamp, sample0=sample0)
+    at = {(int(d), int(t)): i for i, (d, t) in enumerate(zip(res["dmi"], res["t"]))}
+    per = nchan // nsb
+    for c in cands:
+        i = at[(c["dmi"], c["peak_idx"] - sample0)]
+        first, count = bands[int(res["band"][i])]
+        edges = [fch1 + (first * per - 0.5) * foff, fch1 + ((first + count) * per - 0.5) * foff]
+        c.update(band=(int(first), int(count)), f_lo=float(min(edges)), f_hi=float(max(edges)), snr_full=float(res["snr_full"][i]))
+    return cands
