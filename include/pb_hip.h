@@ -310,6 +310,63 @@ int pb_correlate_gated(pb_handle *h, int stream, int nseg, const int32_t *row0, 
                        float *vis, int32_t *rows_used);
 int pb_correlate_timers(const pb_handle *h, float *ms2);
 
+/* ---- imager: gated visibilities summed over delay hypotheses (reference: analysis/loc_step2.py :91-120, the scan of
+ * each baseline's cross power over fractional delays, and analysis/loc_step3.py :287-348, every baseline's delay on a
+ * sky grid).  Both are one operation: for each hypothesis (a "pixel": one delay and one phase per baseline) rotate each
+ * baseline's 4096-channel visibility by the hypothesis's delay slope, add the channels, combine the baselines.  The
+ * object is independent of pb_handle (like pb_search): the caller's visibilities are uploaded once and stay on the
+ * device while they are imaged on any number of grids.
+ * Definition, operation by operation (THIS project's own; tests/image_ref.py restates it in binary32 and binary64):
+ *   inputs     u[b][s][c] = (ur, ui): the caller's weighted visibility of baseline b = 0..nbl-1, product slot s = 0, 1,
+ *              channel c = 0..4095 (bin k = 2155 + c of the 12500-point FFT).  dd[p][b]: the delay tried for baseline b
+ *              at pixel p in samples at 128 MS/s -- how much LATER the second antenna of the baseline sees the signal;
+ *              dpsi[p][b]: a phase in turns (NULL: 0).  Both binary64.
+ *   phase      in binary64, every operation rounded once, none contracted:
+ *                  t = dpsi[p][b] + (double)k * (dd[p][b] / 12500.0)        r64 = t - rint(t)   (rint: ties to even)
+ *              and r = (float)r64, |r| <= 0.5 turns.
+ *   rotation   (cr, sr) ~ (cos 2 pi r, sin 2 pi r) by a fixed polynomial, every line one binary32 operation (plain
+ *              multiplies and adds, no fma), the hardware's sine and cosine are not used:
+ *                  q  = rintf(4.0f * r)                  (-2 .. 2: the nearest quarter turn; exact)
+ *                  f  = r - q * 0.25f                    (|f| <= 1/8; both operations exact)
+ *                  f2 = f * f
+ *                  sn = (((S3 * f2 + S2) * f2 + S1) * f2 + S0) * f
+ *                  cs = (((C4 * f2 + C3) * f2 + C2) * f2 + C1) * f2 + 1.0f
+ *                  S0 =  0x1.921fb6p+2f   S1 = -0x1.4abbbap+5f   S2 =  0x1.465ec4p+6f   S3 = -0x1.2d9b7cp+6f
+ *                  C1 = -0x1.3bd3ccp+4f   C2 =  0x1.03c1dep+6f   C3 = -0x1.55c64ap+6f   C4 =  0x1.d9f188p+5f
+ *                  (cr, sr) = (cs, sn), (-sn, cs), (-cs, -sn), (sn, -cs) for ((int)q & 3) = 0, 1, 2, 3
+ *              Largest absolute error against binary64 over every multiple of 2^-20 in [-0.5, 0.5] and 10^6 random r:
+ *              0.37 x 2^-22 (tests/test_image_ref_cpu.py holds it to 2^-22).
+ *   one term   every line one binary32 operation, left to right (the shape of the correlator's term):
+ *                  zr = ur*cr + ui*sr          zi = ui*cr - ur*sr
+ *              i.e. u exp(-2 pi i r): with u = V_ij = X_i conj(X_j) of the correlator the sum peaks where dd is
+ *              d_j - d_i, the delay of antenna j behind antenna i.
+ *   channels   per (p, b, s): lane l = 0..63 starts from (+0.0f, +0.0f) and adds the terms of channels l, l + 64, ..,
+ *              l + 4032 in that order, re and im separately; then P[l] = P[l] + P[l + o] for o = 32, 16, 8, 4, 2, 1
+ *              (the __shfl_down tree); lane 0 holds z(p, b, s).  The order depends on nothing else.
+ *   per_bl     the z values, float32 [npix][nbl][2][2] (re, im).
+ *   image      image[p] starts from +0.0f and adds, for b ascending and s = 0 then 1, in binary32:
+ *                  PB_IMAGE_DELAY   sqrtf(zr*zr + zi*zi)   (two multiplies, an add, the correctly rounded root)
+ *                  PB_IMAGE_PHASE   zr
+ *              No atomics anywhere: the order is the definition.
+ *   pb_imager_create   1 <= nbl <= 256, max_pix >= 1: allocates the device buffers (the visibilities, and max_pix rows
+ *                      of delays, phases, z values and image values).  No HIP device: PB_EHIP.
+ *   pb_imager_set_vis  u: host float32 [nbl][2][4096][2]; returns when it has been copied.
+ *   pb_imager_run      1 <= npix <= max_pix; dd, dpsi: host binary64 [npix][nbl]; image (host [npix]) and per_bl may be
+ *                      NULL.  Returns when the outputs have arrived.
+ *   pb_imager_timers   device time of the last run in ms: upload of dd and dpsi; the kernels; the copy back.
+ * Refused with a message (pb_imager_last_error; of a failed create: pb_imager_last_error(NULL)): PB_EINVAL for nbl,
+ * max_pix, npix or mode out of range, a missing dd, and -- checked on the host before anything is queued -- a dd or dpsi
+ * that is not finite or a |dd| > 2^24; PB_ESTATE for a run before pb_imager_set_vis. */
+typedef struct pb_imager pb_imager;
+#define PB_IMAGE_DELAY 0
+#define PB_IMAGE_PHASE 1
+int pb_imager_create(int device, int nbl, int max_pix, pb_imager **out);
+void pb_imager_destroy(pb_imager *m);
+const char *pb_imager_last_error(const pb_imager *m);
+int pb_imager_set_vis(pb_imager *m, const float *u);
+int pb_imager_run(pb_imager *m, int mode, int npix, const double *dd, const double *dpsi, float *image, float *per_bl);
+int pb_imager_timers(const pb_imager *m, float *ms3);
+
 int pb_profile(pb_handle *h, int enable);
 int pb_get_timers(pb_handle *h, pb_timers *out, int reset);
 int pb_debug_fetch(pb_handle *h, int what, int ant, int seg, void *dst, size_t nbytes);

@@ -18,5 +18,7 @@ Only the hot path of the reference's process_baseband executable lives here:
   gulp.py          GulpSearch, the search over a stream in gulps
   candidates.py    the host's grouping of points into candidates, the candidate line, the TCP leg to the coincidencer
   triggers.py      trigger_t wire format towards the voltage dumper
+  correlate.py     visibilities and lag delays of a set of antennas' voltage dumps (pb_correlate*)
+  localise.py      fine delays and a sky position from those visibilities (pb_imager_*)
 """
 __version__ = "0.1"

@@ -62,8 +62,12 @@ EXPORTS = ["pb_config_default", "pb_create", "pb_destroy", "pb_last_error", "pb_
            "pb_search_gulp_run", "pb_search_gulp_advance", "pb_search_gulp_fetch", "pb_search_gulp_timers", "pb_search_set_pol",
            "pb_search_pol", "pb_search_pol_cutouts", "pb_search_pol_fetch", "pb_search_pol_timers", "pb_search_set_subbands",
            "pb_search_subbands", "pb_search_subband_dm", "pb_search_subband_timers", "pb_search_set_rfi_chan",
-           "pb_search_rfi_chan_info", "pb_correlate_info", "pb_correlate", "pb_correlate_gated", "pb_correlate_timers"]
+           "pb_search_rfi_chan_info", "pb_correlate_info", "pb_correlate", "pb_correlate_gated", "pb_correlate_timers",
+           "pb_imager_create", "pb_imager_destroy", "pb_imager_last_error", "pb_imager_set_vis", "pb_imager_run",
+           "pb_imager_timers"]
 CORR_RAW, CORR_KUR = 0, 1
+IMAGE_DELAY, IMAGE_PHASE = 0, 1
+IMAGE_PX = 8                 # pixels of the imaging kernel's tile (csrc/pb_image.hip: IMG_PX)
 
 _lib = None
 
@@ -187,6 +191,14 @@ def load():
     L.pb_correlate.argtypes = [vp, C.c_int, C.c_int, C.c_int, fp, i32p, ip]
     L.pb_correlate_gated.argtypes = [vp, C.c_int, C.c_int, i32p, C.c_int, C.c_int, fp, i32p]
     L.pb_correlate_timers.argtypes = [vp, fp]
+    L.pb_imager_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+    L.pb_imager_destroy.argtypes = [vp]
+    L.pb_imager_destroy.restype = None
+    L.pb_imager_last_error.argtypes = [vp]
+    L.pb_imager_last_error.restype = C.c_char_p
+    L.pb_imager_set_vis.argtypes = [vp, fp]
+    L.pb_imager_run.argtypes = [vp, C.c_int, C.c_int, f64p, f64p, fp, fp]
+    L.pb_imager_timers.argtypes = [vp, fp]
     for n in EXPORTS:
         f = getattr(L, n)
         if f.restype is C.c_int or n in ("pb_create", "pb_query", "pb_sync"):
@@ -475,3 +487,79 @@ class PbHandle(object):
         out = np.empty((nrows, NCHAN), np.complex64)
         self._chk(self._L.pb_channelize_f32(self._h, _f32(x), nrows, taps, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+
+class PbImager(object):
+    """Visibilities imaged over delay hypotheses on the GPU (include/pb_hip.h: pb_imager_*).  nbl baselines (any list of
+    them: the caller's), at most max_pix pixels per run.  The visibilities stay on the device between runs."""
+
+    def __init__(self, nbl, max_pix, device=0):
+        L = load()
+        self._L = L
+        self._m = C.c_void_p()
+        rc = L.pb_imager_create(device, int(nbl), int(max_pix), C.byref(self._m))
+        if rc != 0:
+            msg = L.pb_imager_last_error(None).decode()
+            self._m = None
+            if rc == -22:
+                raise ValueError(msg)
+            raise PbError("pb_imager_create failed (%d): %s" % (rc, msg))
+        self.nbl, self.max_pix = int(nbl), int(max_pix)
+
+    def _chk(self, rc):
+        if rc != 0:
+            msg = self._L.pb_imager_last_error(self._m).decode()
+            if rc == -22:
+                raise ValueError(msg)
+            raise PbError("libpb_hip error %d: %s" % (rc, msg))
+
+    def close(self):
+        if getattr(self, "_m", None):
+            self._L.pb_imager_destroy(self._m)
+            self._m = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set_vis(self, u):
+        """u: complex [nbl][2][4096], the caller's weighted visibilities of product slots 0 and 1"""
+        u = np.ascontiguousarray(u, np.complex64)
+        if u.shape != (self.nbl, 2, NCHANOUT):
+            raise ValueError("u must be [%d][2][%d]" % (self.nbl, NCHANOUT))
+        self._chk(self._L.pb_imager_set_vis(self._m, u.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def run(self, dd, dpsi=None, mode="delay", per_baseline=False):
+        """dd (samples the baseline's second antenna is late), dpsi (turns, or None): [npix][nbl] -> image float32
+        [npix], or (image, per_bl complex64 [npix][nbl][2]) with per_baseline"""
+        if mode not in ("delay", "phase"):
+            raise ValueError("mode must be 'delay' or 'phase'")
+        dd = np.ascontiguousarray(dd, np.float64)
+        if dd.ndim != 2 or dd.shape[1] != self.nbl:
+            raise ValueError("dd must be [npix][%d]" % self.nbl)
+        if dpsi is not None:
+            dpsi = np.ascontiguousarray(dpsi, np.float64)
+            if dpsi.shape != dd.shape:
+                raise ValueError("dpsi must have dd's shape")
+        npix = dd.shape[0]
+        image = np.empty(npix, np.float32)
+        per_bl = np.empty((npix, self.nbl, 2), np.complex64) if per_baseline else None
+        f64p = C.POINTER(C.c_double)
+        self._chk(self._L.pb_imager_run(self._m, IMAGE_PHASE if mode == "phase" else IMAGE_DELAY, npix,
+                                        dd.ctypes.data_as(f64p), dpsi.ctypes.data_as(f64p) if dpsi is not None else None,
+                                        _f32(image), per_bl.ctypes.data_as(C.POINTER(C.c_float)) if per_baseline else None))
+        return (image, per_bl) if per_baseline else image
+
+    def timers(self):
+        """device ms of the last run: (upload of dd and dpsi, kernels, copy to the host)"""
+        ms = np.zeros(3, np.float32)
+        self._chk(self._L.pb_imager_timers(self._m, _f32(ms)))
+        return tuple(float(v) for v in ms)
