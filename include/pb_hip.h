@@ -367,6 +367,59 @@ int pb_imager_set_vis(pb_imager *m, const float *u);
 int pb_imager_run(pb_imager *m, int mode, int npix, const double *dd, const double *dpsi, float *image, float *per_bl);
 int pb_imager_timers(const pb_imager *m, float *ms3);
 
+/* ---- beamformer: phased sums of a handle's antennas, detected (reference: analysis/beamforming.py, "classical
+ * beamforming" of an on-pulse against an off-pulse window, :20-24, and analysis/baseband.py apply_filter: per-channel
+ * linear combinations of the antennas' spectra, then detected).  Needs coherence = 1, like the correlator, and uses the
+ * delays that the correlator and the imager measure.
+ * Definition, operation by operation (THIS project's own; tests/beam_ref.py restates it):
+ *   inputs     X[a][p][t][c] exactly as the correlator defines it: the selected set's last batch, stream = PB_CORR_RAW or
+ *              PB_CORR_KUR, t = seg * rows_per_seg + row, 0 <= t < T = nseg * rows_per_seg, bin k = 2155 + c.
+ *              Per beam b = 0..nbeam-1 and antenna a (arrays [nbeam][nant], row-major):
+ *                  delay[b][a]   binary64, samples at 128 MS/s that antenna a is LATE (the convention of
+ *                                correlate.fit_delays' delay_samples and localise.antenna_delays)
+ *                  psi[b][a]     binary64, turns; NULL: 0
+ *                  gain[b][a]    binary32; NULL: 1.0f.  0 drops the antenna; a one-hot row is a single-antenna beam.
+ *              Per channel: shift[c], int32 >= 0, the first row of output sample 0 (NULL: 0) -- output samples may follow
+ *              a dispersed pulse (correlate.dm_row0).  tscr >= 1 rows per output sample, nout >= 1 output samples.
+ *   weight     one per (b, a, c), the same for every row.  The phase is the imager's, in binary64, every operation
+ *              rounded once:
+ *                  t = psi[b][a] + (double)k * (delay[b][a] / 12500.0)      r = (float)(t - rint(t))
+ *              (cr, sr) = the imager's rotation polynomial of r (the lines and coefficients above; the hardware's sine
+ *              and cosine are not used), then, each one binary32 operation:
+ *                  wr = gain * cr              wi = gain * sr
+ *   voltage    per (b, p, t, c): Yr = Yi = +0.0f, then for a = 0 .. nant-1 ascending, with x = X[a][p][t][c], every line
+ *              one binary32 operation, no contraction:
+ *                  tr = xr*wr - xi*wi          ti = xi*wr + xr*wi
+ *                  Yr = Yr + tr                Yi = Yi + ti
+ *              i.e. x exp(+2 pi i r): an antenna that is d samples late carries exp(-2 pi i k d / 12500), so the true
+ *              delays align the antennas.  Antennas of gain 0 are still added; their terms are +-0.
+ *   detection  per (b, t, c), with A = (Ar, Ai) the voltage of pol 0 and B that of pol 1: the correlator's term lines in
+ *              the order AA BB CR CI, no normalisation:
+ *                  AA = Ar*Ar + Ai*Ai    BB = Br*Br + Bi*Bi    CR = Ar*Br + Ai*Bi    CI = Ai*Br - Ar*Bi
+ *   integration out[b][s][q][c], q = 0..3, starts from +0.0f and adds the rows shift[c] + s * tscr + (0 .. tscr - 1) IN
+ *              ROW ORDER, in binary32.  A window may cross segment boundaries; nothing splits a window's rows; no
+ *              atomics: the order is the definition and depends on neither nbeam nor the launch.
+ *   rows_used  int32 per (b, s, c).  Raw stream: tscr.  Excised stream: the number of the window's rows whose row weight
+ *              (as pb_fetch's `weights`) is > 0 for every antenna with gain[b][a] != 0.  Rows of weight 0 are still
+ *              added -- their spectra are zero.
+ * Outputs (host memory, either may be NULL): beams float32 [nbeam][nout][4][4096] -- one beam's block has the layout of a
+ * `nifs 4` filterbank at fp32 --; rows_used int32 [nbeam][nout][4096].
+ *   pb_beamform         runs on the SELECTED set, on a stream of its own behind that set's channeliser and detect, and
+ *                       returns when its outputs have arrived.  The library owns and grows its device buffers (the
+ *                       weights, the outputs, the row counts) and frees them in pb_destroy; pb_query's device_bytes grows
+ *                       by them.  No other state of the handle changes: what pb_fetch returns afterwards is what it
+ *                       returns without the call.
+ *   pb_beamform_timers  device time of the last call in ms: the uploads, weights and row counts; the beam kernel; the
+ *                       copy to the host.
+ * Refused, with a pb_last_error text, on the host before anything is queued: PB_EINVAL for coherence = 0, nant > 8, a
+ * stream the handle's rfi_mode does not produce, nseg / tscr / nout <= 0, nbeam outside 1..64, a NULL delay, a delay, psi
+ * or gain that is not finite, |delay| > 2^24, a shift < 0, a window that leaves the batch (max(shift) + nout * tscr > T),
+ * outputs beyond 2 GiB; PB_ESTATE for nseg above what the set's last pb_process processed, or no pb_process on the set
+ * yet. */
+int pb_beamform(pb_handle *h, int stream, int nseg, int nbeam, const double *delay, const double *psi,
+                const float *gain, const int32_t *shift, int tscr, int nout, float *beams, int32_t *rows_used);
+int pb_beamform_timers(const pb_handle *h, float *ms3);
+
 int pb_profile(pb_handle *h, int enable);
 int pb_get_timers(pb_handle *h, pb_timers *out, int reset);
 int pb_debug_fetch(pb_handle *h, int what, int ant, int seg, void *dst, size_t nbytes);

@@ -1,0 +1,212 @@
+"""Coherent beams from the voltage dumps of a set of antennas.
+
+The phased sums run on the GPU (include/pb_hip.h: pb_beamform, over the spectra that a coherence = 1 handle keeps);
+everything in this module is host-side numpy on small arrays:
+
+  read_beams(path, nant)           a text file of beams, one line of nant delays (samples) per beam
+  loc_delays(path, nant)           the per-antenna delays that the localise tool measured (its fit_samples)
+  one_hot(nant)                    the delays (0) and gains of the nant single-antenna beams
+  ratio(series, incoherent)        a beam's summed power over that of the incoherent sum
+
+Command line (offline; the dump files are those the hosts' --replay reads, read as the correlate tool reads them):
+
+  python -m vlite-fast_amd.beamform --replay ant0.uw ant1.uw ... [--offsets n0 n1 ...] [--stream raw|kur]
+         (--delays d0 d1 ... | --beams beams.txt | --loc loc.npz) [--phase-turns] [--dm DM] [--tscr N]
+         [--rows-per-seg N] [--max-seg N] [--seconds N] -o beams.npz
+  (--rows-per-seg R --max-seg S: the handle's batch, 1024 x 10 rows = one second by default; a file's tail that does not
+  fill a batch is left out.  Per batch the tool emits the output samples whose whole window -- in every channel, with
+  the shift of --dm -- lies within the batch: the correlate tool's limit for its gates, and an output sample is never
+  split between two calls)
+
+A delay is the number of samples at 128 MS/s that the antenna is LATE (correlate's delay_samples, localise's
+fit_samples and antenna_delays); --phase-turns adds localise.phase_turns of the delays as the beams' phases (the
+-384 MHz x delay that a geometric or cable delay in front of the sampler carries; a shift of the sample stream, as
+--offsets makes, carries none).  --dm makes the output samples follow a pulse of that dispersion measure:
+shift = correlate.dm_row0(dm, 0, ...).  The tool always appends the nant single-antenna beams (one-hot gains, delay 0)
+to the call; their sum is the incoherent beam.
+
+beams.npz: beams float32 [nbeam][nout][4][4096] (the coherent beams' AA, BB, CR, CI dynamic spectra, tscr rows per
+sample), sample_row int64 [nout] (the first row, counted from the start of the data, of each output sample in channel
+0; channel c starts shift[c] rows later), shift int32 [4096], rows_used int32 [nbeam][nout][4096], incoherent float64
+[nout][4][4096] (the single-antenna beams added), series float64 [nbeam][nout] and incoherent_series float64 [nout]
+(AA + BB added over the band), ratio float64 [nbeam] (sum of series / sum of incoherent_series), delays and
+phase_turns float64 [nbeam][nant], freqs_mhz [4096], tscr, options (JSON).
+"""
+import argparse
+import importlib
+import json
+import sys
+
+import numpy as np
+
+NFFT, NCHANOUT = 12500, 4096
+
+
+def _corr():
+    return importlib.import_module("vlite-fast_amd.correlate")
+
+
+def read_beams(path, nant):
+    """float64 [nbeam][nant] from a text file: one line of nant delays per beam, '#' starts a comment"""
+    rows = []
+    with open(path) as f:
+        for n, line in enumerate(f, 1):
+            words = line.split("#")[0].split()
+            if not words:
+                continue
+            if len(words) != nant:
+                raise ValueError("%s:%d: %d delays, %d antennas" % (path, n, len(words), nant))
+            rows.append([float(w) for w in words])
+    if not rows:
+        raise ValueError("%s holds no beam" % path)
+    return np.array(rows, np.float64)
+
+
+def loc_delays(path, nant):
+    """float64 [1][nant]: localise's fit_samples [2 slots][nant] (samples later than antenna 0), the slots averaged"""
+    z = np.load(path)
+    if "fit_samples" not in z.files:
+        raise ValueError("%s holds no fit_samples" % path)
+    fit = np.asarray(z["fit_samples"], np.float64)
+    if fit.ndim != 2 or fit.shape[1] != nant:
+        raise ValueError("%s: fit_samples is %s, %d antennas" % (path, fit.shape, nant))
+    return fit.mean(axis=0)[None]
+
+
+def one_hot(nant):
+    """(delay float64 [nant][nant] = 0, gain float32 [nant][nant] = the unit matrix)"""
+    return np.zeros((nant, nant), np.float64), np.eye(nant, dtype=np.float32)
+
+
+def ratio(series, incoherent_series):
+    """sum of a beam's series over the sum of the incoherent one; series [..][nout]"""
+    return np.asarray(series, np.float64).sum(axis=-1) / float(np.sum(incoherent_series))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the tool
+
+def make_parser():
+    p = argparse.ArgumentParser(prog="beamform", description="coherent beams from voltage dumps")
+    p.add_argument("--replay", nargs="+", required=True, help="one dump file per antenna (antenna = position)")
+    p.add_argument("--offsets", nargs="+", type=int, default=None, help="samples to advance each antenna by (>= 0)")
+    p.add_argument("--stream", choices=("raw", "kur"), default="raw")
+    g = p.add_mutually_exclusive_group(required=True)
+    g.add_argument("--delays", nargs="+", type=float, default=None, help="one beam: samples that each antenna is late")
+    g.add_argument("--beams", default=None, help="text file, one line of delays per beam")
+    g.add_argument("--loc", default=None, help="the localise tool's npz: its fit_samples")
+    p.add_argument("--phase-turns", action="store_true", help="add localise.phase_turns of the delays as phases")
+    p.add_argument("--dm", type=float, default=None, help="output samples follow a pulse of this DM")
+    p.add_argument("--tscr", type=int, default=8, help="rows per output sample")
+    p.add_argument("--seconds", type=int, default=0, help="stop after this many seconds (0 = all)")
+    p.add_argument("--rows-per-seg", type=int, default=1024, help="FFT rows per segment of the handle (a multiple of 8)")
+    p.add_argument("--max-seg", type=int, default=10, help="segments per batch (1024 x 10 = one second)")
+    p.add_argument("--device", type=int, default=0)
+    p.add_argument("-o", "--output", required=True)
+    return p
+
+
+def parse_args(argv=None):
+    p = make_parser()
+    a = p.parse_args(argv)
+    n = len(a.replay)
+    if n > 8:
+        p.error("at most 8 antennas")
+    if a.offsets is None:
+        a.offsets = [0] * n
+    if len(a.offsets) != n or min(a.offsets) < 0:
+        p.error("--offsets: one value >= 0 per --replay file")
+    if a.delays is not None and len(a.delays) != n:
+        p.error("--delays: one value per --replay file")
+    if a.delays is not None and not np.all(np.isfinite(a.delays)):
+        p.error("--delays must be finite")
+    if a.rows_per_seg <= 0 or a.rows_per_seg % 8 or a.max_seg <= 0:
+        p.error("--rows-per-seg must be a positive multiple of 8, --max-seg positive")
+    if a.tscr <= 0 or a.tscr > a.rows_per_seg * a.max_seg or a.seconds < 0:
+        p.error("--tscr must be 1 .. the %d rows of a batch, --seconds not negative" % (a.rows_per_seg * a.max_seg))
+    if a.dm is not None and a.dm < 0:
+        p.error("--dm must not be negative")
+    return a
+
+
+def beam_table(args):
+    """the beams of the command line: (delay float64 [nbeam][nant], psi float64 [nbeam][nant] or None)"""
+    nant = len(args.replay)
+    if args.delays is not None:
+        delay = np.array([args.delays], np.float64)
+    elif args.beams is not None:
+        delay = read_beams(args.beams, nant)
+    else:
+        delay = loc_delays(args.loc, nant)
+    if delay.shape[0] + nant > 64:
+        raise ValueError("at most %d beams beside the %d single-antenna ones" % (64 - nant, nant))
+    psi = None
+    if args.phase_turns:
+        psi = importlib.import_module("vlite-fast_amd.localise").phase_turns(delay)
+    return delay, psi
+
+
+def run(args):
+    lp = importlib.import_module("vlite-fast_amd.libpb")
+    corr = _corr()
+    nant = len(args.replay)
+    R, S, tscr = args.rows_per_seg, args.max_seg, args.tscr
+    T = R * S
+    stream = lp.CORR_KUR if args.stream == "kur" else lp.CORR_RAW
+    try:
+        delay, psi = beam_table(args)
+        shift = None
+        if args.dm is not None:
+            shift = corr.dm_row0(args.dm, 0, T - tscr + 1)
+    except (ValueError, IOError) as e:
+        raise SystemExit("beamform: %s" % e)
+    nb = delay.shape[0]
+    nout = (T - (0 if shift is None else int(shift.max()))) // tscr            # per batch
+    # the call's beams: the coherent ones, then the single-antenna ones
+    d1, g1 = one_hot(nant)
+    all_delay = np.concatenate([delay, d1])
+    all_psi = None if psi is None else np.concatenate([psi, np.zeros_like(d1)])
+    all_gain = np.concatenate([np.ones(delay.shape, np.float32), g1])
+    ants = [corr._Antenna(p, o) for p, o in zip(args.replay, args.offsets)]
+    beams, used, incoherent, rows = [], [], [], []
+    nbatch = 0
+    max_batches = -(-args.seconds * 10240 // T) if args.seconds else 0
+    with lp.PbHandle(device=args.device, nant=nant, nbit=8, npol=2, rfi_mode=2 if stream else 0, rows_per_seg=R,
+                     max_seg=S, coherence=True) as h:
+        while not max_batches or nbatch < max_batches:
+            blocks = [a.take(T * NFFT) for a in ants]
+            if any(b is None for b in blocks):
+                break
+            for k, b in enumerate(blocks):
+                for s in range(S):
+                    h.submit_planar(k, s, b[0, s * R * NFFT:(s + 1) * R * NFFT], b[1, s * R * NFFT:(s + 1) * R * NFFT])
+            h.process(S)
+            v, u = h.beamform(stream, S, all_delay, all_psi, all_gain, shift, tscr, nout)
+            beams.append(v[:nb].copy())
+            used.append(u[:nb].copy())
+            incoherent.append(v[nb:].astype(np.float64).sum(axis=0))
+            rows.append(nbatch * T + tscr * np.arange(nout, dtype=np.int64))
+            nbatch += 1
+    if nbatch == 0:
+        raise SystemExit("beamform: the files hold less than one batch of %d rows" % T)
+    beams = np.concatenate(beams, axis=1)
+    incoherent = np.concatenate(incoherent, axis=0)
+    series = beams[:, :, :2].astype(np.float64).sum(axis=(2, 3))
+    inc_series = incoherent[:, :2].sum(axis=(1, 2))
+    out = dict(beams=beams, sample_row=np.concatenate(rows),
+               shift=np.zeros(NCHANOUT, np.int32) if shift is None else shift.astype(np.int32),
+               rows_used=np.concatenate(used, axis=1), incoherent=incoherent, series=series, incoherent_series=inc_series,
+               ratio=ratio(series, inc_series), delays=delay, phase_turns=np.zeros_like(delay) if psi is None else psi,
+               freqs_mhz=corr.chan_freqs_mhz(), tscr=np.int64(tscr),
+               options=np.array(json.dumps(vars(args), sort_keys=True)))
+    np.savez(args.output, **out)
+    return out
+
+
+def main(argv=None):
+    run(parse_args(argv))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

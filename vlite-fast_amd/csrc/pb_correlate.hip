@@ -201,20 +201,6 @@ static void corr_launch_all(CorrArgs a, int ngate, hipStream_t st)
     }
 }
 
-template <class T> static hipError_t corr_grow(pb_handle *h, T **p, size_t *cap, size_t n)
-{
-    if (n <= *cap) return hipSuccess;
-    if (*p) {
-        (void)hipFree(*p);
-        h->device_bytes -= *cap * sizeof(T);
-        *p = nullptr;
-        *cap = 0;
-    }
-    hipError_t e = dmalloc(h, p, n);
-    if (e == hipSuccess) *cap = n;
-    return e;
-}
-
 void pb_correlate_free(pb_handle *h)
 {
     pb_corr_state *cs = h->corr;
@@ -257,11 +243,11 @@ static int corr_run(pb_handle *h, int stream, int nseg, int ngate, int nrows, fl
         HIPCHK(h, hipStreamCreateWithFlags(&cs->st, hipStreamNonBlocking));
         for (hipEvent_t &e : cs->ev) HIPCHK(h, hipEventCreate(&e));
     }
-    if (vis) HIPCHK(h, corr_grow(h, &cs->d_vis, &cs->vis_cap, nvis));
-    if (rows_used) HIPCHK(h, corr_grow(h, &cs->d_used, &cs->used_cap, nused));
-    HIPCHK(h, corr_grow(h, &cs->d_row0, &cs->row0_cap, (size_t)ngate * PB_NCHANOUT));
+    if (vis) HIPCHK(h, dgrow(h, &cs->d_vis, &cs->vis_cap, nvis));
+    if (rows_used) HIPCHK(h, dgrow(h, &cs->d_used, &cs->used_cap, nused));
+    HIPCHK(h, dgrow(h, &cs->d_row0, &cs->row0_cap, (size_t)ngate * PB_NCHANOUT));
     const bool kur = stream == PB_CORR_KUR;
-    if (kur && rows_used) HIPCHK(h, corr_grow(h, &cs->d_pref, &cs->pref_cap, (size_t)nbl * (T + 1)));
+    if (kur && rows_used) HIPCHK(h, dgrow(h, &cs->d_pref, &cs->pref_cap, (size_t)nbl * (T + 1)));
 
     const pb_handle::BufSet &b = h->set();
     // behind the set's channeliser and detect (ev_chan); whatever refills the set is queued by a later call, and this

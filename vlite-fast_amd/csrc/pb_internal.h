@@ -124,6 +124,7 @@ struct pb_handle {
     hipStream_t s_coadd = nullptr;   // stream of pb_coadd_local / pb_coadd_finish (nullptr: the main stream)
     int coadd_slot = 0, coadd_last = 0;
     struct pb_corr_state *corr = nullptr;   // the correlator's stream, events and output buffers (pb_correlate.hip), lazily
+    struct pb_beam_state *beam = nullptr;   // the beamformer's (pb_beamform.hip), lazily
     FftTables ft = {};
     DagConsts dag = {}, dag_fb = {};   // D'Agostino constants for N = 500 (blocks) and N = 12500 (FFT rows, K4)
     int dag_bands = 0;               // 1: crossings located (flags decided without the cube root); -1: PB_DAG_BANDS=0; -2: search failed, fallback
@@ -160,6 +161,7 @@ struct StreamScope {
 PB_LOCAL int fail(pb_handle *h, int code, const std::string &msg);   // h = nullptr: the error pb_create reports
 PB_LOCAL hipError_t sync_all(pb_handle *h);
 PB_LOCAL void pb_correlate_free(pb_handle *h);                       // pb_correlate.hip: what pb_destroy releases
+PB_LOCAL void pb_beamform_free(pb_handle *h);                        // pb_beamform.hip: likewise
 
 template <class T>
 static hipError_t dmalloc(pb_handle *h, T **p, size_t n)
@@ -167,6 +169,22 @@ static hipError_t dmalloc(pb_handle *h, T **p, size_t n)
     if (n == 0) { *p = nullptr; return hipSuccess; }
     hipError_t e = hipMalloc((void **)p, n * sizeof(T));
     if (e == hipSuccess) h->device_bytes += n * sizeof(T);
+    return e;
+}
+
+// a buffer the library owns and grows on demand (*cap in elements); device_bytes follows it
+template <class T>
+static hipError_t dgrow(pb_handle *h, T **p, size_t *cap, size_t n)
+{
+    if (n <= *cap) return hipSuccess;
+    if (*p) {
+        (void)hipFree(*p);
+        h->device_bytes -= *cap * sizeof(T);
+        *p = nullptr;
+        *cap = 0;
+    }
+    hipError_t e = dmalloc(h, p, n);
+    if (e == hipSuccess) *cap = n;
     return e;
 }
 
