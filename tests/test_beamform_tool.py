@@ -53,8 +53,9 @@ def test_beam_tables(tmp_path):
         f.write("# three antennas\n0 58 131.5\n\n0 -58 -131.5   # negated\n")
     args = b.parse_args(["--replay", "a", "b", "c", "--beams", path, "--phase-turns", "-o", "x"])
     delay, psi = b.beam_table(args)
-    assert delay.tolist() == [[0, 58, 131.5], [0, -58, -131.5]] and np.array_equal(psi, loc.phase_turns(delay))
-    assert np.array_equal(psi, -3.0 * delay)
+    # psi is added to an antenna's phase: it takes off what phase_turns says the antenna carries
+    assert delay.tolist() == [[0, 58, 131.5], [0, -58, -131.5]] and np.array_equal(psi, -loc.phase_turns(delay))
+    assert np.array_equal(psi, 3.0 * delay)
     with pytest.raises(ValueError, match="2 delays, 3 antennas"):
         open(path, "a").write("1 2\n")
         b.read_beams(path, 3)

@@ -19,9 +19,12 @@ Command line (offline; the dump files are those the hosts' --replay reads, read 
   split between two calls)
 
 A delay is the number of samples at 128 MS/s that the antenna is LATE (correlate's delay_samples, localise's
-fit_samples and antenna_delays); --phase-turns adds localise.phase_turns of the delays as the beams' phases (the
--384 MHz x delay that a geometric or cable delay in front of the sampler carries; a shift of the sample stream, as
---offsets makes, carries none).  --dm makes the output samples follow a pulse of that dispersion measure:
+fit_samples and antenna_delays).  An antenna d samples late carries exp(-2 pi i k d / 12500), which the delay takes
+off, and, where the delay lies in front of the sampler (geometry, cables), localise.phase_turns(d) = -384 MHz x delay
+= -3 d turns on top; a shift of the sample stream, as --offsets makes, carries none.  pb_beamform adds psi to an
+antenna's phase, so --phase-turns passes psi = -localise.phase_turns(delay), which takes that phase off again: the
+same correction as localise.baseline_phase makes for the imager's PHASE mode (tests/test_array_conventions_cpu.py holds
+the two to each other).  --dm makes the output samples follow a pulse of that dispersion measure:
 shift = correlate.dm_row0(dm, 0, ...).  The tool always appends the nant single-antenna beams (one-hot gains, delay 0)
 to the call; their sum is the incoherent beam.
 
@@ -29,8 +32,9 @@ beams.npz: beams float32 [nbeam][nout][4][4096] (the coherent beams' AA, BB, CR,
 sample), sample_row int64 [nout] (the first row, counted from the start of the data, of each output sample in channel
 0; channel c starts shift[c] rows later), shift int32 [4096], rows_used int32 [nbeam][nout][4096], incoherent float64
 [nout][4][4096] (the single-antenna beams added), series float64 [nbeam][nout] and incoherent_series float64 [nout]
-(AA + BB added over the band), ratio float64 [nbeam] (sum of series / sum of incoherent_series), delays and
-phase_turns float64 [nbeam][nant], freqs_mhz [4096], tscr, options (JSON).
+(AA + BB added over the band), ratio float64 [nbeam] (sum of series / sum of incoherent_series), delays float64
+[nbeam][nant], phase_turns float64 [nbeam][nant] (the psi handed to pb_beamform, in turns: -localise.phase_turns(delays)
+with --phase-turns, else 0), freqs_mhz [4096], tscr, options (JSON).
 """
 import argparse
 import importlib
@@ -95,7 +99,8 @@ def make_parser():
     g.add_argument("--delays", nargs="+", type=float, default=None, help="one beam: samples that each antenna is late")
     g.add_argument("--beams", default=None, help="text file, one line of delays per beam")
     g.add_argument("--loc", default=None, help="the localise tool's npz: its fit_samples")
-    p.add_argument("--phase-turns", action="store_true", help="add localise.phase_turns of the delays as phases")
+    p.add_argument("--phase-turns", action="store_true",
+                   help="take off the phase localise.phase_turns says a late antenna carries: psi = -phase_turns(delay)")
     p.add_argument("--dm", type=float, default=None, help="output samples follow a pulse of this DM")
     p.add_argument("--tscr", type=int, default=8, help="rows per output sample")
     p.add_argument("--seconds", type=int, default=0, help="stop after this many seconds (0 = all)")
@@ -142,7 +147,8 @@ def beam_table(args):
         raise ValueError("at most %d beams beside the %d single-antenna ones" % (64 - nant, nant))
     psi = None
     if args.phase_turns:
-        psi = importlib.import_module("vlite-fast_amd.localise").phase_turns(delay)
+        # pb_beamform ADDS psi to an antenna's phase: what takes off the phase_turns(d) that an antenna d late carries
+        psi = -importlib.import_module("vlite-fast_amd.localise").phase_turns(delay)
     return delay, psi
 
 
