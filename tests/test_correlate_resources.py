@@ -2,34 +2,19 @@
 prefix kernel and no others, no scratch memory, no LDS, no AGPRs, 8-byte loads of the spectra, no inline assembly."""
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "vlite-fast_amd", "csrc")
-FLAGS = ("-O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt "
-         "-fno-gpu-flush-denormals-to-zero -I../../include -I. -w --cuda-device-only -S -o -").split()
+from kernel_resources import CSRC, HIPCC, compile_usage
+
 # k_correlate<NI, NJ, DIAG>: a group of 1..4 antennas against itself, and group 0 against 1 or 2 antennas of group 1
 KERNELS = ("k_corr_prefix", "k_correlateILi1ELi1ELb1EE", "k_correlateILi2ELi2ELb1EE", "k_correlateILi3ELi3ELb1EE",
            "k_correlateILi4ELi4ELb1EE", "k_correlateILi4ELi1ELb0EE", "k_correlateILi4ELi2ELb0EE")
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 def test_correlate_kernels_use_no_scratch_and_no_lds():
-    r = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["pb_correlate.hip"], cwd=CSRC, stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=900)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    asm = r.stdout.decode()
-    use, cur = {}, None
-    for line in asm.splitlines():
-        m = re.match(r"^(_Z\w+):", line)
-        if m:
-            cur = m.group(1)
-            continue
-        m = re.match(r"^; (NumVgprs|NumAgprs|ScratchSize|Occupancy|LDSByteSize): (\d+)", line)
-        if m and cur:
-            use.setdefault(cur, {})[m.group(1)] = int(m.group(2))
+    use, asm = compile_usage("pb_correlate.hip")
     assert len(use) == len(KERNELS), sorted(use)                    # every kernel of the file is on the list
     for name in KERNELS:
         k = [v for sym, v in use.items() if name in sym]

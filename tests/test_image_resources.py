@@ -1,33 +1,17 @@
 """The imager's kernels' compiled resource usage (no GPU: hipcc cross-compiles gfx950): the two kernels and no others,
 each with its resource lines, and no scratch memory."""
 import os
-import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "vlite-fast_amd", "csrc")
-FLAGS = ("-O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt "
-         "-fno-gpu-flush-denormals-to-zero -I../../include -I. -w --cuda-device-only -S -o -").split()
+from kernel_resources import HIPCC, LINES, compile_usage
+
 KERNELS = ("k_image_z", "k_image_sum")
-LINES = ("NumVgprs", "NumAgprs", "ScratchSize", "Occupancy", "LDSByteSize")
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 def test_image_kernels_use_no_scratch():
-    r = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["pb_image.hip"], cwd=CSRC, stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=900)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    use, cur = {}, None
-    for line in r.stdout.decode().splitlines():
-        m = re.match(r"^(_Z\w+):", line)
-        if m:
-            cur = m.group(1)
-            continue
-        m = re.match(r"^; (%s): (\d+)" % "|".join(LINES), line)
-        if m and cur:
-            use.setdefault(cur, {})[m.group(1)] = int(m.group(2))
+    use, _ = compile_usage("pb_image.hip")
     assert len(use) == len(KERNELS), sorted(use)                    # every kernel of the file is on the list
     for name in KERNELS:
         k = [v for sym, v in use.items() if name in sym]

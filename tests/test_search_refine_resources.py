@@ -1,31 +1,15 @@
 """The refinement kernels' compiled resource usage (no GPU: hipcc cross-compiles gfx950): no scratch memory, LDS within
 what lets several workgroups share a CU, and no inline assembly in their source."""
 import os
-import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "vlite-fast_amd", "csrc")
-FLAGS = ("-O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt "
-         "-fno-gpu-flush-denormals-to-zero -I../../include -I. -w --cuda-device-only -S -o -").split()
+from kernel_resources import CSRC, HIPCC, compile_usage
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 def test_refinement_kernels_use_no_scratch():
-    r = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["search_refine.hip"], cwd=CSRC, stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=900)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    use, cur = {}, None
-    for line in r.stdout.decode().splitlines():
-        m = re.match(r"^(_Z\w+):", line)
-        if m:
-            cur = m.group(1)
-            continue
-        m = re.match(r"^; (NumVgprs|ScratchSize|Occupancy|LDSByteSize): (\d+)", line)
-        if m and cur:
-            use.setdefault(cur, {})[m.group(1)] = int(m.group(2))
+    use, _ = compile_usage("search_refine.hip")
     for name in ("k_refine_series", "k_refine_dm", "k_refine_width"):
         k = [v for sym, v in use.items() if name in sym]
         assert len(k) == 1, name

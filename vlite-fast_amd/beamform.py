@@ -43,7 +43,8 @@ import sys
 
 import numpy as np
 
-NFFT, NCHANOUT = 12500, 4096
+replay_batches = importlib.import_module("vlite-fast_amd.replay_batches")
+NCHANOUT = 4096
 
 
 def _corr():
@@ -88,13 +89,11 @@ def ratio(series, incoherent_series):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# the tool
+# the tool (its common arguments, the dump reader and the batch loop are shared with correlate.py: replay_batches.py)
 
 def make_parser():
     p = argparse.ArgumentParser(prog="beamform", description="coherent beams from voltage dumps")
-    p.add_argument("--replay", nargs="+", required=True, help="one dump file per antenna (antenna = position)")
-    p.add_argument("--offsets", nargs="+", type=int, default=None, help="samples to advance each antenna by (>= 0)")
-    p.add_argument("--stream", choices=("raw", "kur"), default="raw")
+    replay_batches.add_arguments(p)
     g = p.add_mutually_exclusive_group(required=True)
     g.add_argument("--delays", nargs="+", type=float, default=None, help="one beam: samples that each antenna is late")
     g.add_argument("--beams", default=None, help="text file, one line of delays per beam")
@@ -103,30 +102,17 @@ def make_parser():
                    help="take off the phase localise.phase_turns says a late antenna carries: psi = -phase_turns(delay)")
     p.add_argument("--dm", type=float, default=None, help="output samples follow a pulse of this DM")
     p.add_argument("--tscr", type=int, default=8, help="rows per output sample")
-    p.add_argument("--seconds", type=int, default=0, help="stop after this many seconds (0 = all)")
-    p.add_argument("--rows-per-seg", type=int, default=1024, help="FFT rows per segment of the handle (a multiple of 8)")
-    p.add_argument("--max-seg", type=int, default=10, help="segments per batch (1024 x 10 = one second)")
-    p.add_argument("--device", type=int, default=0)
-    p.add_argument("-o", "--output", required=True)
     return p
 
 
 def parse_args(argv=None):
     p = make_parser()
     a = p.parse_args(argv)
-    n = len(a.replay)
-    if n > 8:
-        p.error("at most 8 antennas")
-    if a.offsets is None:
-        a.offsets = [0] * n
-    if len(a.offsets) != n or min(a.offsets) < 0:
-        p.error("--offsets: one value >= 0 per --replay file")
-    if a.delays is not None and len(a.delays) != n:
+    replay_batches.check_arguments(p, a)
+    if a.delays is not None and len(a.delays) != len(a.replay):
         p.error("--delays: one value per --replay file")
     if a.delays is not None and not np.all(np.isfinite(a.delays)):
         p.error("--delays must be finite")
-    if a.rows_per_seg <= 0 or a.rows_per_seg % 8 or a.max_seg <= 0:
-        p.error("--rows-per-seg must be a positive multiple of 8, --max-seg positive")
     if a.tscr <= 0 or a.tscr > a.rows_per_seg * a.max_seg or a.seconds < 0:
         p.error("--tscr must be 1 .. the %d rows of a batch, --seconds not negative" % (a.rows_per_seg * a.max_seg))
     if a.dm is not None and a.dm < 0:
@@ -153,12 +139,10 @@ def beam_table(args):
 
 
 def run(args):
-    lp = importlib.import_module("vlite-fast_amd.libpb")
     corr = _corr()
     nant = len(args.replay)
     R, S, tscr = args.rows_per_seg, args.max_seg, args.tscr
     T = R * S
-    stream = lp.CORR_KUR if args.stream == "kur" else lp.CORR_RAW
     try:
         delay, psi = beam_table(args)
         shift = None
@@ -173,28 +157,13 @@ def run(args):
     all_delay = np.concatenate([delay, d1])
     all_psi = None if psi is None else np.concatenate([psi, np.zeros_like(d1)])
     all_gain = np.concatenate([np.ones(delay.shape, np.float32), g1])
-    ants = [corr._Antenna(p, o) for p, o in zip(args.replay, args.offsets)]
     beams, used, incoherent, rows = [], [], [], []
-    nbatch = 0
-    max_batches = -(-args.seconds * 10240 // T) if args.seconds else 0
-    with lp.PbHandle(device=args.device, nant=nant, nbit=8, npol=2, rfi_mode=2 if stream else 0, rows_per_seg=R,
-                     max_seg=S, coherence=True) as h:
-        while not max_batches or nbatch < max_batches:
-            blocks = [a.take(T * NFFT) for a in ants]
-            if any(b is None for b in blocks):
-                break
-            for k, b in enumerate(blocks):
-                for s in range(S):
-                    h.submit_planar(k, s, b[0, s * R * NFFT:(s + 1) * R * NFFT], b[1, s * R * NFFT:(s + 1) * R * NFFT])
-            h.process(S)
-            v, u = h.beamform(stream, S, all_delay, all_psi, all_gain, shift, tscr, nout)
-            beams.append(v[:nb].copy())
-            used.append(u[:nb].copy())
-            incoherent.append(v[nb:].astype(np.float64).sum(axis=0))
-            rows.append(nbatch * T + tscr * np.arange(nout, dtype=np.int64))
-            nbatch += 1
-    if nbatch == 0:
-        raise SystemExit("beamform: the files hold less than one batch of %d rows" % T)
+    for k, h, stream in replay_batches.batches(args, "beamform"):
+        v, u = h.beamform(stream, S, all_delay, all_psi, all_gain, shift, tscr, nout)
+        beams.append(v[:nb].copy())
+        used.append(u[:nb].copy())
+        incoherent.append(v[nb:].astype(np.float64).sum(axis=0))
+        rows.append(k * T + tscr * np.arange(nout, dtype=np.int64))
     beams = np.concatenate(beams, axis=1)
     incoherent = np.concatenate(incoherent, axis=0)
     series = beams[:, :, :2].astype(np.float64).sum(axis=(2, 3))

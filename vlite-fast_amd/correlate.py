@@ -31,6 +31,7 @@ import sys
 
 import numpy as np
 
+replay_batches = importlib.import_module("vlite-fast_amd.replay_batches")
 NFFT, NCHAN, CHANMIN, NCHANOUT = 12500, 6251, 2155, 4096
 VLITE_RATE = 128000000
 ROW_S = NFFT / float(VLITE_RATE)            # one FFT row: 97.65625 us, 10240 rows per second
@@ -120,40 +121,25 @@ def fit_delays(delays):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# the tool
+# the tool (its common arguments, the dump reader and the batch loop are shared with beamform.py: replay_batches.py)
 
 def make_parser():
     p = argparse.ArgumentParser(prog="correlate", description="visibilities and delays of voltage dumps")
-    p.add_argument("--replay", nargs="+", required=True, help="one dump file per antenna (antenna = position)")
-    p.add_argument("--offsets", nargs="+", type=int, default=None, help="samples to advance each antenna by (>= 0)")
-    p.add_argument("--stream", choices=("raw", "kur"), default="raw")
+    replay_batches.add_arguments(p)
     p.add_argument("--int-rows", type=int, default=1024, help="rows per gate of the ungated correlation")
-    p.add_argument("--seconds", type=int, default=0, help="stop after this many seconds (0 = all)")
     p.add_argument("--dm", type=float, default=None)
     p.add_argument("--t0", type=int, default=None, help="row (from the start of the data) of the pulse in channel 0")
     p.add_argument("--width", type=int, default=None, help="rows per on / off gate")
     p.add_argument("--off-gates", type=int, default=2, help="off gates before and after the on gate")
-    p.add_argument("--rows-per-seg", type=int, default=1024, help="FFT rows per segment of the handle (a multiple of 8)")
-    p.add_argument("--max-seg", type=int, default=10, help="segments per batch (1024 x 10 = one second)")
-    p.add_argument("--device", type=int, default=0)
-    p.add_argument("-o", "--output", required=True)
     return p
 
 
 def parse_args(argv=None):
     p = make_parser()
     a = p.parse_args(argv)
-    n = len(a.replay)
-    if n > 8:
-        p.error("at most 8 antennas")
-    if a.offsets is None:
-        a.offsets = [0] * n
-    if len(a.offsets) != n or min(a.offsets) < 0:
-        p.error("--offsets: one value >= 0 per --replay file")
+    replay_batches.check_arguments(p, a)
     if a.int_rows <= 0 or a.seconds < 0 or a.off_gates < 0:
         p.error("--int-rows must be positive, --seconds and --off-gates not negative")
-    if a.rows_per_seg <= 0 or a.rows_per_seg % 8 or a.max_seg <= 0:
-        p.error("--rows-per-seg must be a positive multiple of 8, --max-seg positive")
     if (a.rows_per_seg * a.max_seg) % a.int_rows:
         p.error("--int-rows must divide the %d rows of a batch" % (a.rows_per_seg * a.max_seg))
     gate = (a.dm, a.t0, a.width)
@@ -165,47 +151,9 @@ def parse_args(argv=None):
     return a
 
 
-class _Antenna(object):
-    """one dump file as a stream of pol-planar samples, its first `offset` samples dropped"""
-    SEC_BYTES = 2 * 25600 * 5032
-
-    def __init__(self, path, offset):
-        dada = importlib.import_module("vlite-fast_amd.dada")
-        self._vdif = importlib.import_module("vlite-fast_amd.vdif")
-        self._ring = dada.FileRing([path])
-        if self._ring.next_header() is None:
-            raise IOError("%s: no header" % path)
-        self._buf = np.empty((2, 0), np.uint8)
-        self._drop = offset
-        self._eod = False
-
-    def take(self, n):
-        """the next n samples per pol, [2][n], or None when the file holds fewer"""
-        while self._buf.shape[1] < n and not self._eod:
-            raw = self._ring.read(self.SEC_BYTES)
-            raw = raw[:len(raw) // (2 * 5032) * (2 * 5032)]
-            if not raw:
-                self._eod = True
-                break
-            d = self._vdif.deframe_block(np.frombuffer(raw, np.uint8))
-            if self._drop:
-                k = min(self._drop, d.shape[1])
-                d = d[:, k:]
-                self._drop -= k
-            self._buf = np.concatenate([self._buf, d], axis=1)
-        if self._buf.shape[1] < n:
-            return None
-        out, self._buf = self._buf[:, :n], self._buf[:, n:]
-        return out
-
-
 def run(args):
-    lp = importlib.import_module("vlite-fast_amd.libpb")
-    nant = len(args.replay)
     R, S = args.rows_per_seg, args.max_seg
-    stream = lp.CORR_KUR if args.stream == "kur" else lp.CORR_RAW
-    ants = [_Antenna(p, o) for p, o in zip(args.replay, args.offsets)]
-    bls = baselines(nant)
+    bls = baselines(len(args.replay))
     vis = np.zeros((len(bls), 4, NCHANOUT), np.complex128)
     rows_used = np.zeros((len(bls), NCHANOUT), np.int64)
     gates = None
@@ -218,26 +166,13 @@ def run(args):
         except ValueError as e:
             raise SystemExit("correlate: the gates must lie within one batch of %d rows (%s)" % (S * R, e))
         gates = dict(batch=batch, row0=row0)
-    nsec = 0                                     # batches done
-    max_batches = -(-args.seconds * 10240 // (S * R)) if args.seconds else 0
-    with lp.PbHandle(device=args.device, nant=nant, nbit=8, npol=2, rfi_mode=2 if stream else 0, rows_per_seg=R,
-                     max_seg=S, coherence=True) as h:
-        while not max_batches or nsec < max_batches:
-            blocks = [a.take(S * R * NFFT) for a in ants]
-            if any(b is None for b in blocks):
-                break
-            for k, b in enumerate(blocks):
-                for s in range(S):
-                    h.submit_planar(k, s, b[0, s * R * NFFT:(s + 1) * R * NFFT], b[1, s * R * NFFT:(s + 1) * R * NFFT])
-            h.process(S)
-            v, u = h.correlate(stream, S, args.int_rows)
-            vis += v.astype(np.complex128).sum(axis=0)
-            rows_used += u.astype(np.int64).sum(axis=0)
-            if gates is not None and gates["batch"] == nsec:
-                gates["vis"], gates["used"] = h.correlate_gated(stream, S, gates["row0"], args.width)
-            nsec += 1
-    if nsec == 0:
-        raise SystemExit("correlate: the files hold less than one batch of %d rows" % (S * R))
+    for k, h, stream in replay_batches.batches(args, "correlate"):
+        v, u = h.correlate(stream, S, args.int_rows)
+        vis += v.astype(np.complex128).sum(axis=0)
+        rows_used += u.astype(np.int64).sum(axis=0)
+        if gates is not None and gates["batch"] == k:
+            gates["vis"], gates["used"] = h.correlate_gated(stream, S, gates["row0"], args.width)
+        nsec = k + 1                             # batches done
     if gates is not None and "vis" not in gates:
         raise SystemExit("correlate: --t0 lies beyond the %d batches read" % nsec)
     lag = lag_delays(vis, used=rows_used)

@@ -18,12 +18,11 @@
 //   accumulators every tscr rows.  A channel's stretch differs from its neighbours' only in its first row (shift): the
 //   addresses are coalesced over the channels whenever neighbouring shifts are equal and correct when they are not.
 //   No LDS, no atomics, no scratch.
-#include "pb_internal.h"
+// Host side: pb_beam_state is a job of csrc/pb_job.h (stream, stage events and times, owned buffers that grow, teardown),
+// and what the call refuses about the handle, the stream and the batch is that header's spectra_check_*.
+#include "pb_job.h"
 #include "rotation_dev.h"
 
-#include <cmath>
-
-#define BEAM_MAX_ANT 8
 #define BEAM_MAX_BEAMS 64
 #define BEAM_TILE 4             // beams of a workgroup
 #define BEAM_CHUNK_ROWS 32      // rows of a workgroup's run: max(1, BEAM_CHUNK_ROWS / tscr) output samples
@@ -38,20 +37,16 @@ struct BeamArgs {
     int S, R, T, nbeam, tscr, nout, spc;   // spc: output samples per workgroup
 };
 
-struct pb_beam_state {
-    hipStream_t st = nullptr;
-    hipEvent_t ev[4] = {};
-    double *d_par = nullptr;             // [2][BEAM_MAX_BEAMS * BEAM_MAX_ANT]: delay / 12500, psi
-    float *d_gain = nullptr;             // [BEAM_MAX_BEAMS * BEAM_MAX_ANT]
-    int32_t *d_shift = nullptr;          // [4096]
-    float2 *d_W = nullptr;
-    float *d_beams = nullptr;
-    int32_t *d_used = nullptr, *d_pref = nullptr;
-    size_t par_cap = 0, gain_cap = 0, shift_cap = 0, W_cap = 0, beams_cap = 0, used_cap = 0, pref_cap = 0;   // elements
+struct PB_LOCAL pb_beam_state : PbJob<3> {      // stages: uploads + weights + row counts, beam kernel, copy to the host
+    DevBuf<double> par;                  // [2][BEAM_MAX_BEAMS * PB_SPECTRA_MAX_ANT]: delay / 12500, psi
+    DevBuf<float> gain;                  // [BEAM_MAX_BEAMS * PB_SPECTRA_MAX_ANT]
+    DevBuf<int32_t> shift;               // [4096]
+    DevBuf<float2> W;
+    DevBuf<float> beams;
+    DevBuf<int32_t> used, pref;
     std::vector<double> h_par;
     std::vector<float> h_gain;
     std::vector<int32_t> h_shift;
-    float ms[3] = {0.f, 0.f, 0.f};
 };
 
 typedef float beam_pair __attribute__((ext_vector_type(2)));      // one value for each of two beams
@@ -256,40 +251,22 @@ static void beam_launch_any(int A, const BeamArgs &a, hipStream_t st)
     }
 }
 
-void pb_beamform_free(pb_handle *h)
-{
-    pb_beam_state *bs = h->beam;
-    if (!bs) return;
-    if (bs->st) { (void)hipStreamSynchronize(bs->st); (void)hipStreamDestroy(bs->st); }
-    for (hipEvent_t e : bs->ev)
-        if (e) (void)hipEventDestroy(e);
-    void *ptrs[] = {bs->d_par, bs->d_gain, bs->d_shift, bs->d_W, bs->d_beams, bs->d_used, bs->d_pref};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    delete bs;
-    h->beam = nullptr;
-}
+void pb_beamform_free(pb_handle *h) { job_free(h->beam); }
 
 extern "C" int pb_beamform(pb_handle *h, int stream, int nseg, int nbeam, const double *delay, const double *psi,
                            const float *gain, const int32_t *shift, int tscr, int nout, float *beams, int32_t *rows_used)
 {
     if (!h) return PB_EINVAL;
     // everything refused is refused here, on the host, before anything is queued
-    if (!h->cfg.coherence) return fail(h, PB_EINVAL, "pb_beamform: the handle keeps no spectra (needs coherence = 1)");
-    if (h->A > BEAM_MAX_ANT) return fail(h, PB_EINVAL, "pb_beamform: at most 8 antennas");
-    if (stream != PB_CORR_RAW && stream != PB_CORR_KUR) return fail(h, PB_EINVAL, "pb_beamform: stream must be 0 (raw) or 1 (excised)");
-    if ((stream == PB_CORR_RAW && h->cfg.rfi_mode == 1) || (stream == PB_CORR_KUR && h->cfg.rfi_mode == 0))
-        return fail(h, PB_EINVAL, "pb_beamform: the handle's rfi_mode does not produce that stream");
-    if (nseg < 1) return fail(h, PB_EINVAL, "pb_beamform: nseg must be positive");
+    if (int rc = spectra_check_config(h, "pb_beamform", stream, nseg)) return rc;
     if (tscr < 1 || nout < 1) return fail(h, PB_EINVAL, "pb_beamform: tscr and nout must be positive");
     if (nbeam < 1 || nbeam > BEAM_MAX_BEAMS) return fail(h, PB_EINVAL, "pb_beamform: nbeam must be 1..64");
     const size_t nused = (size_t)nbeam * nout * PB_NCHANOUT, nval = nused * 4;
-    if (nval * sizeof(float) > ((size_t)2 << 30)) return fail(h, PB_EINVAL, "pb_beamform: outputs beyond 2 GiB; use fewer beams or samples per call");
+    if (!job_output_fits(nval * sizeof(float))) return fail(h, PB_EINVAL, "pb_beamform: outputs beyond 2 GiB; use fewer beams or samples per call");
     if (!delay) return fail(h, PB_EINVAL, "pb_beamform: delay is null");
     const int A = h->A, n = nbeam * A;
     for (int k = 0; k < n; ++k) {
-        if (!std::isfinite(delay[k]) || std::fabs(delay[k]) > 16777216.0)
-            return fail(h, PB_EINVAL, "pb_beamform: a delay is not finite or beyond 2^24 samples");
+        if (!delay_ok(delay[k])) return fail(h, PB_EINVAL, "pb_beamform: a delay is not finite or beyond 2^24 samples");
         if (psi && !std::isfinite(psi[k])) return fail(h, PB_EINVAL, "pb_beamform: a psi is not finite");
         if (gain && !std::isfinite(gain[k])) return fail(h, PB_EINVAL, "pb_beamform: a gain is not finite");
     }
@@ -299,9 +276,7 @@ extern "C" int pb_beamform(pb_handle *h, int stream, int nseg, int nbeam, const 
             if (shift[c] < 0) return fail(h, PB_EINVAL, "pb_beamform: a shift is negative");
             if (shift[c] > max_shift) max_shift = shift[c];
         }
-    const pb_handle::BufSet &b = h->set();
-    if (b.processed < 1) return fail(h, PB_ESTATE, "pb_beamform: no pb_process on the selected set yet");
-    if (nseg > b.processed) return fail(h, PB_ESTATE, "pb_beamform: more segments than the set's last pb_process processed");
+    if (int rc = spectra_check_batch(h, "pb_beamform", nseg)) return rc;
     const int T = nseg * h->R;
     if ((int64_t)max_shift + (int64_t)nout * tscr > T) return fail(h, PB_EINVAL, "pb_beamform: a window leaves the batch's rows");
 
@@ -310,42 +285,39 @@ extern "C" int pb_beamform(pb_handle *h, int stream, int nseg, int nbeam, const 
     bs->h_par.resize(2 * (size_t)n);
     bs->h_gain.resize(n);
     for (int k = 0; k < n; ++k) {
-        bs->h_par[k] = delay[k] / 12500.0;
+        bs->h_par[k] = delay_slope(delay[k]);
         bs->h_par[n + k] = psi ? psi[k] : 0.0;
         bs->h_gain[k] = gain ? gain[k] : 1.0f;
     }
     if (shift) bs->h_shift.assign(shift, shift + PB_NCHANOUT);
     else bs->h_shift.assign(PB_NCHANOUT, 0);
 
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (!bs->st) {
-        HIPCHK(h, hipStreamCreateWithFlags(&bs->st, hipStreamNonBlocking));
-        for (hipEvent_t &e : bs->ev) HIPCHK(h, hipEventCreate(&e));
-    }
+    HIPCHK(h, bs->ensure(h->cfg.device));
     const bool kur = stream == PB_CORR_KUR;
-    HIPCHK(h, dgrow(h, &bs->d_par, &bs->par_cap, (size_t)2 * BEAM_MAX_BEAMS * BEAM_MAX_ANT));
-    HIPCHK(h, dgrow(h, &bs->d_gain, &bs->gain_cap, (size_t)BEAM_MAX_BEAMS * BEAM_MAX_ANT));
-    HIPCHK(h, dgrow(h, &bs->d_shift, &bs->shift_cap, (size_t)PB_NCHANOUT));
-    HIPCHK(h, dgrow(h, &bs->d_W, &bs->W_cap, (size_t)n * PB_NCHANOUT));
-    if (beams) HIPCHK(h, dgrow(h, &bs->d_beams, &bs->beams_cap, nval));
-    if (rows_used) HIPCHK(h, dgrow(h, &bs->d_used, &bs->used_cap, nused));
-    if (kur && rows_used) HIPCHK(h, dgrow(h, &bs->d_pref, &bs->pref_cap, (size_t)nbeam * (T + 1)));
+    HIPCHK(h, bs->par.grow(h, (size_t)2 * BEAM_MAX_BEAMS * PB_SPECTRA_MAX_ANT));
+    HIPCHK(h, bs->gain.grow(h, (size_t)BEAM_MAX_BEAMS * PB_SPECTRA_MAX_ANT));
+    HIPCHK(h, bs->shift.grow(h, (size_t)PB_NCHANOUT));
+    HIPCHK(h, bs->W.grow(h, (size_t)n * PB_NCHANOUT));
+    if (beams) HIPCHK(h, bs->beams.grow(h, nval));
+    if (rows_used) HIPCHK(h, bs->used.grow(h, nused));
+    if (kur && rows_used) HIPCHK(h, bs->pref.grow(h, (size_t)nbeam * (T + 1)));
 
-    // behind the set's channeliser and detect (ev_chan), as the correlator: whatever refills the set is queued by a later
-    // call, and this one returns only when its own stream has drained
+    const pb_handle::BufSet &b = h->set();
+    // behind the set's channeliser and detect (ev_chan): whatever refills the set is queued by a later call, and this
+    // one returns only when its own stream has drained
     HIPCHK(h, hipStreamWaitEvent(bs->st, b.ev_chan, 0));
-    HIPCHK(h, hipEventRecord(bs->ev[0], bs->st));
-    HIPCHK(h, hipMemcpyAsync(bs->d_par, bs->h_par.data(), 2 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, bs->st));
-    HIPCHK(h, hipMemcpyAsync(bs->d_gain, bs->h_gain.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice, bs->st));
-    HIPCHK(h, hipMemcpyAsync(bs->d_shift, bs->h_shift.data(), PB_NCHANOUT * sizeof(int32_t), hipMemcpyHostToDevice, bs->st));
-    k_beam_weights<<<dim3(PB_NCHANOUT / 64, n), 64, 0, bs->st>>>(bs->d_par, bs->d_par + n, bs->d_gain, bs->d_W);
+    HIPCHK(h, bs->mark(0));
+    HIPCHK(h, bs->par.from_host(bs->h_par.data(), 2 * (size_t)n, bs->st));
+    HIPCHK(h, bs->gain.from_host(bs->h_gain.data(), (size_t)n, bs->st));
+    HIPCHK(h, bs->shift.from_host(bs->h_shift.data(), PB_NCHANOUT, bs->st));
+    k_beam_weights<<<dim3(PB_NCHANOUT / 64, n), 64, 0, bs->st>>>(bs->par.p, bs->par.p + n, bs->gain.p, bs->W.p);
     BeamArgs a;
     a.X = (const float2 *)(kur ? b.d_Pkur : b.d_Praw);
-    a.W = bs->d_W;
-    a.shift = bs->d_shift;
+    a.W = bs->W.p;
+    a.shift = bs->shift.p;
     a.pref = nullptr;
-    a.beams = beams ? bs->d_beams : nullptr;
-    a.used = rows_used ? bs->d_used : nullptr;
+    a.beams = beams ? bs->beams.p : nullptr;
+    a.used = rows_used ? bs->used.p : nullptr;
     a.S = h->S;
     a.R = h->R;
     a.T = T;
@@ -354,19 +326,15 @@ extern "C" int pb_beamform(pb_handle *h, int stream, int nseg, int nbeam, const 
     a.nout = nout;
     a.spc = tscr >= BEAM_CHUNK_ROWS ? 1 : BEAM_CHUNK_ROWS / tscr;
     if (kur && rows_used) {
-        k_beam_prefix<<<nbeam, 64, 0, bs->st>>>(b.d_wrow, bs->d_gain, A, (size_t)h->S * h->R, T, bs->d_pref);
-        a.pref = bs->d_pref;
+        k_beam_prefix<<<nbeam, 64, 0, bs->st>>>(b.d_wrow, bs->gain.p, A, (size_t)h->S * h->R, T, bs->pref.p);
+        a.pref = bs->pref.p;
     }
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(bs->ev[1], bs->st));
+    HIPCHK(h, bs->launched(1));
     if (beams || rows_used) beam_launch_any(A, a, bs->st);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(bs->ev[2], bs->st));
-    if (beams) HIPCHK(h, hipMemcpyAsync(beams, bs->d_beams, nval * sizeof(float), hipMemcpyDeviceToHost, bs->st));
-    if (rows_used) HIPCHK(h, hipMemcpyAsync(rows_used, bs->d_used, nused * sizeof(int32_t), hipMemcpyDeviceToHost, bs->st));
-    HIPCHK(h, hipEventRecord(bs->ev[3], bs->st));
-    HIPCHK(h, hipStreamSynchronize(bs->st));
-    for (int k = 0; k < 3; ++k) HIPCHK(h, hipEventElapsedTime(&bs->ms[k], bs->ev[k], bs->ev[k + 1]));
+    HIPCHK(h, bs->launched(2));
+    HIPCHK(h, bs->beams.to_host(beams, nval, bs->st));
+    HIPCHK(h, bs->used.to_host(rows_used, nused, bs->st));
+    HIPCHK(h, bs->finish());
     return PB_OK;
 }
 

@@ -13,9 +13,9 @@
 //   (k_correlate<4, N, false>: 4 N baselines).
 // k_corr_prefix: per baseline the running count of rows whose weight is > 0 for both antennas (one wave, ballots), so
 //   that rows_used of the excised stream is a difference of two entries.
-#include "pb_internal.h"
-
-#define CORR_MAX_ANT 8
+// Host side: pb_corr_state is a job of csrc/pb_job.h (stream, stage events and times, owned buffers that grow, teardown),
+// and what the calls refuse about the handle, the stream and the batch is that header's spectra_check_*.
+#include "pb_job.h"
 
 struct CorrArgs {
     const float2 *X;       // one stream's spectra [A][S][2][R][4096]
@@ -27,14 +27,10 @@ struct CorrArgs {
     int i0, j0;            // first antenna of the tile's rows and columns
 };
 
-struct pb_corr_state {
-    hipStream_t st = nullptr;
-    hipEvent_t ev[3] = {};
-    float *d_vis = nullptr;
-    int32_t *d_used = nullptr, *d_row0 = nullptr, *d_pref = nullptr;
-    size_t vis_cap = 0, used_cap = 0, row0_cap = 0, pref_cap = 0;      // elements
+struct PB_LOCAL pb_corr_state : PbJob<2> {      // stages: kernels, copy to the host
+    DevBuf<float> vis;
+    DevBuf<int32_t> used, row0, pref;
     std::vector<int32_t> h_row0;
-    float ms[2] = {0.f, 0.f};
 };
 
 namespace {
@@ -201,67 +197,34 @@ static void corr_launch_all(CorrArgs a, int ngate, hipStream_t st)
     }
 }
 
-void pb_correlate_free(pb_handle *h)
-{
-    pb_corr_state *cs = h->corr;
-    if (!cs) return;
-    if (cs->st) { (void)hipStreamSynchronize(cs->st); (void)hipStreamDestroy(cs->st); }
-    for (hipEvent_t e : cs->ev)
-        if (e) (void)hipEventDestroy(e);
-    void *ptrs[] = {cs->d_vis, cs->d_used, cs->d_row0, cs->d_pref};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    delete cs;
-    h->corr = nullptr;
-}
-
-// what both entry points refuse before they look at the gates
-static int corr_check(pb_handle *h, const char *what, int stream, int nseg)
-{
-    const std::string w(what);
-    if (!h->cfg.coherence) return fail(h, PB_EINVAL, w + ": the handle keeps no spectra (needs coherence = 1)");
-    if (h->A > CORR_MAX_ANT) return fail(h, PB_EINVAL, w + ": at most 8 antennas");
-    if (stream != PB_CORR_RAW && stream != PB_CORR_KUR) return fail(h, PB_EINVAL, w + ": stream must be 0 (raw) or 1 (excised)");
-    if ((stream == PB_CORR_RAW && h->cfg.rfi_mode == 1) || (stream == PB_CORR_KUR && h->cfg.rfi_mode == 0))
-        return fail(h, PB_EINVAL, w + ": the handle's rfi_mode does not produce that stream");
-    if (nseg < 1) return fail(h, PB_EINVAL, w + ": nseg must be positive");
-    const pb_handle::BufSet &b = h->set();
-    if (b.processed < 1) return fail(h, PB_ESTATE, w + ": no pb_process on the selected set yet");
-    if (nseg > b.processed) return fail(h, PB_ESTATE, w + ": more segments than the set's last pb_process processed");
-    return PB_OK;
-}
+void pb_correlate_free(pb_handle *h) { job_free(h->corr); }
 
 // row0 is in h->corr->h_row0, checked: upload, launch, copy out, wait
 static int corr_run(pb_handle *h, int stream, int nseg, int ngate, int nrows, float *vis, int32_t *rows_used)
 {
     pb_corr_state *cs = h->corr;
     const int nbl = h->A * (h->A + 1) / 2, T = nseg * h->R;
-    const size_t nused = (size_t)ngate * nbl * PB_NCHANOUT, nvis = nused * 8;
-    if (nvis * sizeof(float) > ((size_t)2 << 30)) return fail(h, PB_EINVAL, "pb_correlate: outputs beyond 2 GiB; use fewer gates per call");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (!cs->st) {
-        HIPCHK(h, hipStreamCreateWithFlags(&cs->st, hipStreamNonBlocking));
-        for (hipEvent_t &e : cs->ev) HIPCHK(h, hipEventCreate(&e));
-    }
-    if (vis) HIPCHK(h, dgrow(h, &cs->d_vis, &cs->vis_cap, nvis));
-    if (rows_used) HIPCHK(h, dgrow(h, &cs->d_used, &cs->used_cap, nused));
-    HIPCHK(h, dgrow(h, &cs->d_row0, &cs->row0_cap, (size_t)ngate * PB_NCHANOUT));
+    const size_t nrow0 = (size_t)ngate * PB_NCHANOUT, nused = nrow0 * nbl, nvis = nused * 8;
+    if (!job_output_fits(nvis * sizeof(float))) return fail(h, PB_EINVAL, "pb_correlate: outputs beyond 2 GiB; use fewer gates per call");
     const bool kur = stream == PB_CORR_KUR;
-    if (kur && rows_used) HIPCHK(h, dgrow(h, &cs->d_pref, &cs->pref_cap, (size_t)nbl * (T + 1)));
+    HIPCHK(h, cs->ensure(h->cfg.device));
+    if (vis) HIPCHK(h, cs->vis.grow(h, nvis));
+    if (rows_used) HIPCHK(h, cs->used.grow(h, nused));
+    HIPCHK(h, cs->row0.grow(h, nrow0));
+    if (kur && rows_used) HIPCHK(h, cs->pref.grow(h, (size_t)nbl * (T + 1)));
 
     const pb_handle::BufSet &b = h->set();
     // behind the set's channeliser and detect (ev_chan); whatever refills the set is queued by a later call, and this
     // one returns only when its own stream has drained
     HIPCHK(h, hipStreamWaitEvent(cs->st, b.ev_chan, 0));
-    HIPCHK(h, hipMemcpyAsync(cs->d_row0, cs->h_row0.data(), (size_t)ngate * PB_NCHANOUT * sizeof(int32_t),
-                             hipMemcpyHostToDevice, cs->st));
-    HIPCHK(h, hipEventRecord(cs->ev[0], cs->st));
+    HIPCHK(h, cs->row0.from_host(cs->h_row0.data(), nrow0, cs->st));
+    HIPCHK(h, cs->mark(0));
     CorrArgs a;
     a.X = (const float2 *)(kur ? b.d_Pkur : b.d_Praw);
-    a.row0 = cs->d_row0;
+    a.row0 = cs->row0.p;
     a.pref = nullptr;
-    a.vis = vis ? (float2 *)cs->d_vis : nullptr;
-    a.used = rows_used ? cs->d_used : nullptr;
+    a.vis = vis ? (float2 *)cs->vis.p : nullptr;
+    a.used = rows_used ? cs->used.p : nullptr;
     a.A = h->A;
     a.S = h->S;
     a.R = h->R;
@@ -269,18 +232,14 @@ static int corr_run(pb_handle *h, int stream, int nseg, int ngate, int nrows, fl
     a.nrows = nrows;
     a.i0 = a.j0 = 0;
     if (kur && rows_used) {
-        k_corr_prefix<<<dim3(h->A, h->A), 64, 0, cs->st>>>(b.d_wrow, h->A, (size_t)h->S * h->R, T, cs->d_pref);
-        a.pref = cs->d_pref;
+        k_corr_prefix<<<dim3(h->A, h->A), 64, 0, cs->st>>>(b.d_wrow, h->A, (size_t)h->S * h->R, T, cs->pref.p);
+        a.pref = cs->pref.p;
     }
     corr_launch_all(a, ngate, cs->st);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(cs->ev[1], cs->st));
-    if (vis) HIPCHK(h, hipMemcpyAsync(vis, cs->d_vis, nvis * sizeof(float), hipMemcpyDeviceToHost, cs->st));
-    if (rows_used) HIPCHK(h, hipMemcpyAsync(rows_used, cs->d_used, nused * sizeof(int32_t), hipMemcpyDeviceToHost, cs->st));
-    HIPCHK(h, hipEventRecord(cs->ev[2], cs->st));
-    HIPCHK(h, hipStreamSynchronize(cs->st));
-    HIPCHK(h, hipEventElapsedTime(&cs->ms[0], cs->ev[0], cs->ev[1]));
-    HIPCHK(h, hipEventElapsedTime(&cs->ms[1], cs->ev[1], cs->ev[2]));
+    HIPCHK(h, cs->launched(1));
+    HIPCHK(h, cs->vis.to_host(vis, nvis, cs->st));
+    HIPCHK(h, cs->used.to_host(rows_used, nused, cs->st));
+    HIPCHK(h, cs->finish());
     return PB_OK;
 }
 
@@ -296,7 +255,8 @@ extern "C" int pb_correlate_gated(pb_handle *h, int stream, int nseg, const int3
                                   float *vis, int32_t *rows_used)
 {
     if (!h) return PB_EINVAL;
-    if (int rc = corr_check(h, "pb_correlate_gated", stream, nseg)) return rc;
+    if (int rc = spectra_check_config(h, "pb_correlate_gated", stream, nseg)) return rc;
+    if (int rc = spectra_check_batch(h, "pb_correlate_gated", nseg)) return rc;
     if (ngate <= 0 || nrows <= 0) return fail(h, PB_EINVAL, "pb_correlate_gated: ngate and nrows must be positive");
     if (!row0) return fail(h, PB_EINVAL, "pb_correlate_gated: row0 is null");
     const int T = nseg * h->R;
@@ -311,7 +271,8 @@ extern "C" int pb_correlate_gated(pb_handle *h, int stream, int nseg, const int3
 extern "C" int pb_correlate(pb_handle *h, int stream, int nseg, int int_rows, float *vis, int32_t *rows_used, int *ngate)
 {
     if (!h) return PB_EINVAL;
-    if (int rc = corr_check(h, "pb_correlate", stream, nseg)) return rc;
+    if (int rc = spectra_check_config(h, "pb_correlate", stream, nseg)) return rc;
+    if (int rc = spectra_check_batch(h, "pb_correlate", nseg)) return rc;
     const int T = nseg * h->R;
     if (int_rows <= 0 || T % int_rows) return fail(h, PB_EINVAL, "pb_correlate: int_rows must be positive and divide the batch's rows");
     const int ng = T / int_rows;

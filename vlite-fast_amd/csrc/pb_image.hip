@@ -10,10 +10,10 @@
 //   64 steps the __shfl_down tree of the definition, and lane 0 stores z as one 16-byte value per pixel.
 // k_image_sum: one lane per pixel adds the moduli (or real parts) of its baselines in the definition's order.
 // No LDS, no atomics, no scratch.
-#include "pb_internal.h"
+// Host side: pb_imager is a job of csrc/pb_job.h (stream, stage events and times, owned buffers, teardown); it has no
+// handle, so its errors go through img_fail / g_imager_err and its buffers are allocated once, at create.
+#include "pb_job.h"
 #include "rotation_dev.h"      // img_rotation: the header's binary32 polynomial
-
-#include <cmath>
 
 #define IMG_PX 8            // pixels of a workgroup's tile (libpb.py: IMAGE_PX)
 #define IMG_MAX_NBL 256
@@ -26,17 +26,14 @@ struct ImgArgs {
     int npix, nbl;
 };
 
-struct pb_imager {
+struct PB_LOCAL pb_imager : PbJob<3> {      // stages: upload of dd and dpsi, kernels, copy to the host
     int device = 0, nbl = 0, max_pix = 0;
     bool has_vis = false;
-    hipStream_t st = nullptr;
-    hipEvent_t ev[4] = {};
-    float2 *d_u = nullptr;
-    double *d_q = nullptr, *d_psi = nullptr;
-    float4 *d_z = nullptr;
-    float *d_img = nullptr;
+    DevBuf<float2> u;
+    DevBuf<double> q, psi;
+    DevBuf<float4> z;
+    DevBuf<float> img;
     std::vector<double> h_q, h_psi;
-    float ms[3] = {0.f, 0.f, 0.f};
     std::string err;
 };
 
@@ -47,15 +44,6 @@ static int img_fail(pb_imager *m, int rc, const std::string &what)
     (m ? m->err : g_imager_err) = what;
     return rc;
 }
-
-#define IMGCHK(m, call)                                                        \
-    do {                                                                       \
-        hipError_t e_ = (call);                                                \
-        if (e_ != hipSuccess) {                                                \
-            (m)->err = std::string(#call) + ": " + hipGetErrorString(e_);      \
-            return PB_EHIP;                                                    \
-        }                                                                      \
-    } while (0)
 
 __global__ __launch_bounds__(64) void k_image_z(ImgArgs a)
 {
@@ -144,15 +132,12 @@ extern "C" int pb_imager_create(int device, int nbl, int max_pix, pb_imager **ou
     m->nbl = nbl;
     m->max_pix = max_pix;
     const size_t n = (size_t)max_pix * nbl;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&m->st, hipStreamNonBlocking);
-    for (hipEvent_t &ev : m->ev)
-        if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e == hipSuccess) e = hipMalloc(&m->d_u, (size_t)nbl * 2 * PB_NCHANOUT * sizeof(float2));
-    if (e == hipSuccess) e = hipMalloc(&m->d_q, n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&m->d_psi, n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&m->d_z, n * sizeof(float4));
-    if (e == hipSuccess) e = hipMalloc(&m->d_img, (size_t)max_pix * sizeof(float));
+    hipError_t e = m->ensure(device);
+    if (e == hipSuccess) e = m->u.alloc((size_t)nbl * 2 * PB_NCHANOUT);
+    if (e == hipSuccess) e = m->q.alloc(n);
+    if (e == hipSuccess) e = m->psi.alloc(n);
+    if (e == hipSuccess) e = m->z.alloc(n);
+    if (e == hipSuccess) e = m->img.alloc((size_t)max_pix);
     if (e != hipSuccess) {
         img_fail(nullptr, PB_EHIP, std::string("pb_imager_create: ") + hipGetErrorString(e));
         pb_imager_destroy(m);
@@ -166,13 +151,7 @@ extern "C" void pb_imager_destroy(pb_imager *m)
 {
     if (!m) return;
     (void)hipSetDevice(m->device);
-    if (m->st) { (void)hipStreamSynchronize(m->st); (void)hipStreamDestroy(m->st); }
-    for (hipEvent_t e : m->ev)
-        if (e) (void)hipEventDestroy(e);
-    void *ptrs[] = {m->d_u, m->d_q, m->d_psi, m->d_z, m->d_img};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    delete m;
+    job_free(m);
 }
 
 extern "C" const char *pb_imager_last_error(const pb_imager *m) { return m ? m->err.c_str() : g_imager_err.c_str(); }
@@ -181,9 +160,9 @@ extern "C" int pb_imager_set_vis(pb_imager *m, const float *u)
 {
     if (!m) return img_fail(nullptr, PB_EINVAL, "pb_imager_set_vis: no imager");
     if (!u) return img_fail(m, PB_EINVAL, "pb_imager_set_vis: u is null");
-    IMGCHK(m, hipSetDevice(m->device));
-    IMGCHK(m, hipMemcpyAsync(m->d_u, u, (size_t)m->nbl * 2 * PB_NCHANOUT * sizeof(float2), hipMemcpyHostToDevice, m->st));
-    IMGCHK(m, hipStreamSynchronize(m->st));
+    HIPCHK(m, hipSetDevice(m->device));
+    HIPCHK(m, m->u.from_host((const float2 *)u, m->u.cap, m->st));
+    HIPCHK(m, hipStreamSynchronize(m->st));
     m->has_vis = true;
     return PB_OK;
 }
@@ -200,33 +179,29 @@ extern "C" int pb_imager_run(pb_imager *m, int mode, int npix, const double *dd,
     m->h_q.resize(n);
     m->h_psi.resize(n);
     for (size_t k = 0; k < n; ++k) {
-        if (!std::isfinite(dd[k]) || std::fabs(dd[k]) > 16777216.0)
-            return img_fail(m, PB_EINVAL, "pb_imager_run: a dd is not finite or beyond 2^24 samples");
+        if (!delay_ok(dd[k])) return img_fail(m, PB_EINVAL, "pb_imager_run: a dd is not finite or beyond 2^24 samples");
         if (dpsi && !std::isfinite(dpsi[k])) return img_fail(m, PB_EINVAL, "pb_imager_run: a dpsi is not finite");
-        m->h_q[k] = dd[k] / 12500.0;
+        m->h_q[k] = delay_slope(dd[k]);
         m->h_psi[k] = dpsi ? dpsi[k] : 0.0;
     }
-    IMGCHK(m, hipSetDevice(m->device));
-    IMGCHK(m, hipEventRecord(m->ev[0], m->st));
-    IMGCHK(m, hipMemcpyAsync(m->d_q, m->h_q.data(), n * sizeof(double), hipMemcpyHostToDevice, m->st));
-    IMGCHK(m, hipMemcpyAsync(m->d_psi, m->h_psi.data(), n * sizeof(double), hipMemcpyHostToDevice, m->st));
-    IMGCHK(m, hipEventRecord(m->ev[1], m->st));
+    HIPCHK(m, hipSetDevice(m->device));
+    HIPCHK(m, m->mark(0));
+    HIPCHK(m, m->q.from_host(m->h_q.data(), n, m->st));
+    HIPCHK(m, m->psi.from_host(m->h_psi.data(), n, m->st));
+    HIPCHK(m, m->mark(1));
     ImgArgs a;
-    a.u = m->d_u;
-    a.q = m->d_q;
-    a.psi = m->d_psi;
-    a.z = m->d_z;
+    a.u = m->u.p;
+    a.q = m->q.p;
+    a.psi = m->psi.p;
+    a.z = m->z.p;
     a.npix = npix;
     a.nbl = m->nbl;
     k_image_z<<<dim3((npix + IMG_PX - 1) / IMG_PX, m->nbl), 64, 0, m->st>>>(a);
-    if (image) k_image_sum<<<(npix + 63) / 64, 64, 0, m->st>>>(m->d_z, npix, m->nbl, mode, m->d_img);
-    IMGCHK(m, hipGetLastError());
-    IMGCHK(m, hipEventRecord(m->ev[2], m->st));
-    if (image) IMGCHK(m, hipMemcpyAsync(image, m->d_img, (size_t)npix * sizeof(float), hipMemcpyDeviceToHost, m->st));
-    if (per_bl) IMGCHK(m, hipMemcpyAsync(per_bl, m->d_z, n * sizeof(float4), hipMemcpyDeviceToHost, m->st));
-    IMGCHK(m, hipEventRecord(m->ev[3], m->st));
-    IMGCHK(m, hipStreamSynchronize(m->st));
-    for (int k = 0; k < 3; ++k) IMGCHK(m, hipEventElapsedTime(&m->ms[k], m->ev[k], m->ev[k + 1]));
+    if (image) k_image_sum<<<(npix + 63) / 64, 64, 0, m->st>>>(m->z.p, npix, m->nbl, mode, m->img.p);
+    HIPCHK(m, m->launched(2));
+    HIPCHK(m, m->img.to_host(image, (size_t)npix, m->st));
+    HIPCHK(m, m->z.to_host(per_bl, n, m->st));
+    HIPCHK(m, m->finish());
     return PB_OK;
 }
 

@@ -123,8 +123,8 @@ struct pb_handle {
     hipEvent_t ev_coadd[2] = {};
     hipStream_t s_coadd = nullptr;   // stream of pb_coadd_local / pb_coadd_finish (nullptr: the main stream)
     int coadd_slot = 0, coadd_last = 0;
-    struct pb_corr_state *corr = nullptr;   // the correlator's stream, events and output buffers (pb_correlate.hip), lazily
-    struct pb_beam_state *beam = nullptr;   // the beamformer's (pb_beamform.hip), lazily
+    struct pb_corr_state *corr = nullptr;   // the correlator's job (pb_job.h; pb_correlate.hip), from its first call on
+    struct pb_beam_state *beam = nullptr;   // the beamformer's (pb_beamform.hip), likewise
     FftTables ft = {};
     DagConsts dag = {}, dag_fb = {};   // D'Agostino constants for N = 500 (blocks) and N = 12500 (FFT rows, K4)
     int dag_bands = 0;               // 1: crossings located (flags decided without the cube root); -1: PB_DAG_BANDS=0; -2: search failed, fallback
@@ -148,7 +148,8 @@ struct StreamScope {
     ~StreamScope() { h->stream = saved; }
 };
 
-// ---- what pb_api.hip and pb_coadd.hip share (defined in pb_api.hip unless inline here) ----
+// ---- what the library's files share (defined in pb_api.hip unless inline here); on top of it, pb_job.h: the host side
+// of the calls that run beside the pipeline on a stream of their own (correlator, beamformer, imager) ----
 #define HIPCHK(h, call)                                                                   \
     do {                                                                                  \
         hipError_t e_ = (call);                                                           \
