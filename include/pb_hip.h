@@ -420,6 +420,44 @@ int pb_beamform(pb_handle *h, int stream, int nseg, int nbeam, const double *del
                 const float *gain, const int32_t *shift, int tscr, int nout, float *beams, int32_t *rows_used);
 int pb_beamform_timers(const pb_handle *h, float *ms3);
 
+/* ---- projecting beamformer: pb_beamform with a free complex weight per (beam, pol, antenna, channel), given as the
+ * beam's steering weights put through a matrix per (pol, channel) (reference: analysis/baseband.py apply_filter,
+ * :859-908, and do_filter, :1015-1067: per channel the antennas' spectra through P = I - v v^H / (v^H v), v the
+ * dominant eigenvector of their correlation matrix, i.e. an interferer's direction projected out; the reference filters
+ * one VDIF thread, i.e. one pol, at a time, and so does this).  vlite-fast_amd/nulling.py makes such P from the
+ * correlator's visibilities; any per-pol, per-channel calibration of the beams is the same call.
+ * Definition, operation by operation (THIS project's own; tests/beamproj_ref.py restates it).  Everything pb_beamform
+ * defines -- inputs, delay, psi, gain, shift, tscr, nout, the output layout -- holds here; in addition
+ *   proj       host float32 [2][4096][nant][nant][2]: pol p, channel c, row a, column j, (re, im).  Any finite complex
+ *              matrix per (pol, channel); it need be neither Hermitian nor a projector.
+ *   steering   s[b][a][c] = (sr, si) is exactly pb_beamform's weight (wr, wi): the binary64 phase, the rotation
+ *              polynomial's (cos, sin), sr = gain * cos, si = gain * sin.
+ *   weight     one per (b, p, j, c): (ur, ui) = (+0.0f, +0.0f), then for a = 0 .. nant-1 ascending, with
+ *              (pr, pi) = proj[p][c][a][j], every line one binary32 operation, no contraction:
+ *                  tr = sr*pr - si*pi          ti = si*pr + sr*pi
+ *                  ur = ur + tr                ui = ui + ti
+ *              i.e. w' = s^T P, so that the beam voltage sum_j w'_j x_j is s^T (P x): apply_filter's
+ *              einsum('ij,jk->ik', P, x) followed by the beam.  With P the unit matrix w' equals s as a number (signs of
+ *              zero may differ), and the beams are pb_beamform's.
+ *   voltage    pb_beamform's lines for antennas j = 0 .. nant-1 ascending, pol p with (wr, wi) = w'[b][p][j][c].
+ *   detection, integration   pb_beamform's lines.
+ *   rows_used  int32 per (b, s, c).  Raw stream: tscr.  Excised stream: the number of the window's rows whose row weight
+ *              is > 0 for EVERY antenna of the handle: a matrix mixes the antennas, so a gain of 0 no longer takes an
+ *              antenna out of the count (pb_beamform counts the antennas of non-zero gain only).  The same for every beam.
+ * Outputs as pb_beamform's (host memory, either may be NULL).
+ *   pb_beamform_proj         runs on the SELECTED set as pb_beamform does and returns when its outputs have arrived.  The
+ *                            library owns and grows its device buffers (the matrices, the weights, the outputs, the row
+ *                            counts: its own, not pb_beamform's) and frees them in pb_destroy; pb_query's device_bytes
+ *                            grows by them.  No other state of the handle changes.
+ *   pb_beamform_proj_timers  device time of the last call in ms: the uploads, weights and row counts; the beam kernel;
+ *                            the copy to the host.
+ * Refused, with a pb_last_error text under this call's name, on the host before anything is queued: everything
+ * pb_beamform refuses, and PB_EINVAL for a NULL proj or a proj value that is not finite. */
+int pb_beamform_proj(pb_handle *h, int stream, int nseg, int nbeam, const double *delay, const double *psi,
+                     const float *gain, const float *proj, const int32_t *shift, int tscr, int nout,
+                     float *beams, int32_t *rows_used);
+int pb_beamform_proj_timers(const pb_handle *h, float *ms3);
+
 int pb_profile(pb_handle *h, int enable);
 int pb_get_timers(pb_handle *h, pb_timers *out, int reset);
 int pb_debug_fetch(pb_handle *h, int what, int ant, int seg, void *dst, size_t nbytes);

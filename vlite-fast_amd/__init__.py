@@ -21,6 +21,7 @@ Only the hot path of the reference's process_baseband executable lives here:
   correlate.py     visibilities and lag delays of a set of antennas' voltage dumps (pb_correlate*)
   localise.py      fine delays and a sky position from those visibilities (pb_imager_*)
   beamform.py      coherent beams of those antennas at such delays, beside their incoherent sum (pb_beamform)
+  nulling.py       per-pol, per-channel projectors that take interferers out of those beams (pb_beamform_proj)
   replay_batches.py  what those two tools share: their common arguments, the dump reader, the batch loop over a handle
 """
 __version__ = "0.1"

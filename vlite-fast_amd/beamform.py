@@ -12,7 +12,8 @@ Command line (offline; the dump files are those the hosts' --replay reads, read 
 
   python -m vlite-fast_amd.beamform --replay ant0.uw ant1.uw ... [--offsets n0 n1 ...] [--stream raw|kur]
          (--delays d0 d1 ... | --beams beams.txt | --loc loc.npz) [--phase-turns] [--dm DM] [--tscr N]
-         [--rows-per-seg N] [--max-seg N] [--seconds N] -o beams.npz
+         [--rows-per-seg N] [--max-seg N] [--seconds N] [--null K [--null-min-ratio X] [--null-train ROW0 ROW1]]
+         -o beams.npz
   (--rows-per-seg R --max-seg S: the handle's batch, 1024 x 10 rows = one second by default; a file's tail that does not
   fill a batch is left out.  Per batch the tool emits the output samples whose whole window -- in every channel, with
   the shift of --dm -- lies within the batch: the correlate tool's limit for its gates, and an output sample is never
@@ -28,13 +29,21 @@ the two to each other).  --dm makes the output samples follow a pulse of that di
 shift = correlate.dm_row0(dm, 0, ...).  The tool always appends the nant single-antenna beams (one-hot gains, delay 0)
 to the call; their sum is the incoherent beam.
 
+--null K takes the K strongest directions per (pol, channel) out of the coherent beams (nulling.py; DESIGN.md section
+13): per batch the tool correlates the batch's rows -- all of them, or the batch-relative rows ROW0 .. ROW1 - 1 of
+--null-train, which can leave a pulse out -- in gates of at most one segment, as the correlate tool does, builds the
+projectors (with --null-min-ratio X only in channels whose largest eigenvalue is at least X times the mean of the
+others) and forms the coherent beams with pb_beamform_proj.  The single-antenna beams stay un-nulled, through
+pb_beamform, so `incoherent` and `ratio` mean what they mean without --null.
+
 beams.npz: beams float32 [nbeam][nout][4][4096] (the coherent beams' AA, BB, CR, CI dynamic spectra, tscr rows per
 sample), sample_row int64 [nout] (the first row, counted from the start of the data, of each output sample in channel
 0; channel c starts shift[c] rows later), shift int32 [4096], rows_used int32 [nbeam][nout][4096], incoherent float64
 [nout][4][4096] (the single-antenna beams added), series float64 [nbeam][nout] and incoherent_series float64 [nout]
 (AA + BB added over the band), ratio float64 [nbeam] (sum of series / sum of incoherent_series), delays float64
 [nbeam][nant], phase_turns float64 [nbeam][nant] (the psi handed to pb_beamform, in turns: -localise.phase_turns(delays)
-with --phase-turns, else 0), freqs_mhz [4096], tscr, options (JSON).
+with --phase-turns, else 0), freqs_mhz [4096], tscr, options (JSON).  With --null also null_count int64 [2][4096], the vectors nulled per (pol,
+channel), added over the batches, and rows_used counts every antenna (pb_beamform_proj's).
 """
 import argparse
 import importlib
@@ -102,6 +111,12 @@ def make_parser():
                    help="take off the phase localise.phase_turns says a late antenna carries: psi = -phase_turns(delay)")
     p.add_argument("--dm", type=float, default=None, help="output samples follow a pulse of this DM")
     p.add_argument("--tscr", type=int, default=8, help="rows per output sample")
+    p.add_argument("--null", type=int, default=None, metavar="K",
+                   help="project the K strongest directions per (pol, channel) out of the coherent beams")
+    p.add_argument("--null-min-ratio", type=float, default=None, metavar="X",
+                   help="null only where the largest eigenvalue is at least X times the mean of the others")
+    p.add_argument("--null-train", nargs=2, type=int, default=None, metavar=("ROW0", "ROW1"),
+                   help="rows ROW0 .. ROW1 - 1 of each batch make the matrices (default: all)")
     return p
 
 
@@ -117,6 +132,14 @@ def parse_args(argv=None):
         p.error("--tscr must be 1 .. the %d rows of a batch, --seconds not negative" % (a.rows_per_seg * a.max_seg))
     if a.dm is not None and a.dm < 0:
         p.error("--dm must not be negative")
+    if a.null is None and (a.null_min_ratio is not None or a.null_train is not None):
+        p.error("--null-min-ratio and --null-train need --null")
+    if a.null is not None and not 1 <= a.null <= len(a.replay) - 1:
+        p.error("--null must be 1 .. the number of antennas less one")
+    if a.null_min_ratio is not None and not a.null_min_ratio > 0:
+        p.error("--null-min-ratio must be positive")
+    if a.null_train is not None and not 0 <= a.null_train[0] < a.null_train[1] <= a.rows_per_seg * a.max_seg:
+        p.error("--null-train: 0 <= ROW0 < ROW1 <= the %d rows of a batch" % (a.rows_per_seg * a.max_seg))
     return a
 
 
@@ -158,11 +181,23 @@ def run(args):
     all_psi = None if psi is None else np.concatenate([psi, np.zeros_like(d1)])
     all_gain = np.concatenate([np.ones(delay.shape, np.float32), g1])
     beams, used, incoherent, rows = [], [], [], []
+    nulling = importlib.import_module("vlite-fast_amd.nulling") if args.null is not None else None
+    null_count = np.zeros((2, NCHANOUT), np.int64)
     for k, h, stream in replay_batches.batches(args, "beamform"):
-        v, u = h.beamform(stream, S, all_delay, all_psi, all_gain, shift, tscr, nout)
-        beams.append(v[:nb].copy())
-        used.append(u[:nb].copy())
-        incoherent.append(v[nb:].astype(np.float64).sum(axis=0))
+        if nulling is None:
+            v, u = h.beamform(stream, S, all_delay, all_psi, all_gain, shift, tscr, nout)
+            beams.append(v[:nb].copy())
+            used.append(u[:nb].copy())
+            incoherent.append(v[nb:].astype(np.float64).sum(axis=0))
+        else:
+            r0, r1 = args.null_train if args.null_train is not None else (0, T)
+            cov = nulling.covariances(nulling.training_vis(h, stream, S, r0, r1), nant)
+            proj, count = nulling.projectors(cov, args.null, args.null_min_ratio)
+            null_count += count
+            v, u = h.beamform_proj(stream, S, delay, proj, psi, None, shift, tscr, nout)
+            beams.append(v)
+            used.append(u)
+            incoherent.append(h.beamform(stream, S, d1, None, g1, shift, tscr, nout)[0].astype(np.float64).sum(axis=0))
         rows.append(k * T + tscr * np.arange(nout, dtype=np.int64))
     beams = np.concatenate(beams, axis=1)
     incoherent = np.concatenate(incoherent, axis=0)
@@ -172,8 +207,14 @@ def run(args):
                shift=np.zeros(NCHANOUT, np.int32) if shift is None else shift.astype(np.int32),
                rows_used=np.concatenate(used, axis=1), incoherent=incoherent, series=series, incoherent_series=inc_series,
                ratio=ratio(series, inc_series), delays=delay, phase_turns=np.zeros_like(delay) if psi is None else psi,
-               freqs_mhz=corr.chan_freqs_mhz(), tscr=np.int64(tscr),
-               options=np.array(json.dumps(vars(args), sort_keys=True)))
+               freqs_mhz=corr.chan_freqs_mhz(), tscr=np.int64(tscr))
+    options = vars(args).copy()
+    if nulling is None:
+        for name in ("null", "null_min_ratio", "null_train"):       # without --null the file is what it was
+            del options[name]
+    else:
+        out["null_count"] = null_count
+    out["options"] = np.array(json.dumps(options, sort_keys=True))
     np.savez(args.output, **out)
     return out
 

@@ -64,7 +64,7 @@ EXPORTS = ["pb_config_default", "pb_create", "pb_destroy", "pb_last_error", "pb_
            "pb_search_subbands", "pb_search_subband_dm", "pb_search_subband_timers", "pb_search_set_rfi_chan",
            "pb_search_rfi_chan_info", "pb_correlate_info", "pb_correlate", "pb_correlate_gated", "pb_correlate_timers",
            "pb_imager_create", "pb_imager_destroy", "pb_imager_last_error", "pb_imager_set_vis", "pb_imager_run",
-           "pb_imager_timers", "pb_beamform", "pb_beamform_timers"]
+           "pb_imager_timers", "pb_beamform", "pb_beamform_timers", "pb_beamform_proj", "pb_beamform_proj_timers"]
 CORR_RAW, CORR_KUR = 0, 1
 IMAGE_DELAY, IMAGE_PHASE = 0, 1
 IMAGE_PX = 8                 # pixels of the imaging kernel's tile (csrc/pb_image.hip: IMG_PX)
@@ -201,6 +201,8 @@ def load():
     L.pb_imager_timers.argtypes = [vp, fp]
     L.pb_beamform.argtypes = [vp, C.c_int, C.c_int, C.c_int, f64p, f64p, fp, i32p, C.c_int, C.c_int, fp, i32p]
     L.pb_beamform_timers.argtypes = [vp, fp]
+    L.pb_beamform_proj.argtypes = [vp, C.c_int, C.c_int, C.c_int, f64p, f64p, fp, fp, i32p, C.c_int, C.c_int, fp, i32p]
+    L.pb_beamform_proj_timers.argtypes = [vp, fp]
     for n in EXPORTS:
         f = getattr(L, n)
         if f.restype is C.c_int or n in ("pb_create", "pb_query", "pb_sync"):
@@ -461,6 +463,17 @@ class PbHandle(object):
         (or [nant]: one beam), samples that each antenna is late; psi: turns, gain: float32, both delay's shape or None;
         shift: int32 [4096], the first row of output sample 0 per channel, or None; nout: output samples, by default
         as many as fit.  -> (beams float32 [nbeam][nout][4][4096] (AA, BB, CR, CI), rows_used int32 [nbeam][nout][4096])"""
+        delay, psi, gain, shift, nout, beams, used = self._beam_arguments(nseg, delay, psi, gain, shift, tscr, nout)
+        f64p, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        self._chk(self._L.pb_beamform(self._h, stream, nseg, delay.shape[0], delay.ctypes.data_as(f64p),
+                                      psi.ctypes.data_as(f64p) if psi is not None else None, _f32(gain),
+                                      shift.ctypes.data_as(i32p) if shift is not None else None, tscr, nout,
+                                      _f32(beams), used.ctypes.data_as(i32p)))
+        return beams, used
+
+    def _beam_arguments(self, nseg, delay, psi, gain, shift, tscr, nout):
+        """what beamform and beamform_proj share: the arguments as contiguous arrays of the library's types, nout (by
+        default as many output samples as fit) and the arrays the outputs arrive in"""
         delay = np.ascontiguousarray(np.atleast_2d(np.asarray(delay, np.float64)))
         if delay.ndim != 2 or delay.shape[1] != self.nant:
             raise ValueError("delay must be [nbeam][%d]" % self.nant)
@@ -484,17 +497,36 @@ class PbHandle(object):
         shape = (max(nbeam, 1), max(nout, 1))              # (a refused call still needs arrays to point at)
         beams = np.empty(shape + (4, NCHANOUT), np.float32)
         used = np.empty(shape + (NCHANOUT,), np.int32)
-        f64p, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        self._chk(self._L.pb_beamform(self._h, stream, nseg, nbeam, delay.ctypes.data_as(f64p),
-                                      psi.ctypes.data_as(f64p) if psi is not None else None, _f32(gain),
-                                      shift.ctypes.data_as(i32p) if shift is not None else None, tscr, nout,
-                                      _f32(beams), used.ctypes.data_as(i32p)))
-        return beams, used
+        return delay, psi, gain, shift, nout, beams, used
 
     def beamform_timers(self):
         """device ms of the last beamform call: (uploads + weights + row counts, beam kernel, copy to the host)"""
         ms = np.zeros(3, np.float32)
         self._chk(self._L.pb_beamform_timers(self._h, _f32(ms)))
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
+    # ---- projecting beamformer (include/pb_hip.h: pb_beamform_proj; needs coherence=True)
+    def beamform_proj(self, stream, nseg, delay, proj, psi=None, gain=None, shift=None, tscr=1, nout=None):
+        """beamform() with the antennas' spectra put through a matrix per (pol, channel) first: proj complex64
+        [2][4096][nant][nant] (row a, column j: the beam's weight of antenna j is sum_a s_a proj[a][j], s the weights of
+        beamform()), e.g. nulling.projectors' spatial nulls.  The other arguments and the outputs are beamform()'s; on the
+        excised stream rows_used counts the rows whose weight is > 0 for every antenna, whatever the gains."""
+        delay, psi, gain, shift, nout, beams, used = self._beam_arguments(nseg, delay, psi, gain, shift, tscr, nout)
+        proj = np.ascontiguousarray(proj, np.complex64)
+        if proj.shape != (2, NCHANOUT, self.nant, self.nant):
+            raise ValueError("proj must be [2][%d][%d][%d]" % (NCHANOUT, self.nant, self.nant))
+        f64p, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        self._chk(self._L.pb_beamform_proj(self._h, stream, nseg, delay.shape[0], delay.ctypes.data_as(f64p),
+                                           psi.ctypes.data_as(f64p) if psi is not None else None, _f32(gain),
+                                           proj.ctypes.data_as(C.POINTER(C.c_float)),
+                                           shift.ctypes.data_as(i32p) if shift is not None else None, tscr, nout,
+                                           _f32(beams), used.ctypes.data_as(i32p)))
+        return beams, used
+
+    def beamform_proj_timers(self):
+        """device ms of the last beamform_proj call: (uploads + weights + row counts, beam kernel, copy to the host)"""
+        ms = np.zeros(3, np.float32)
+        self._chk(self._L.pb_beamform_proj_timers(self._h, _f32(ms)))
         return float(ms[0]), float(ms[1]), float(ms[2])
 
     def profile(self, enable=True):
