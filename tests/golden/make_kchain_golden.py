@@ -5,9 +5,9 @@ of every output of oracle.segment -- raw and excised codes, the fp32 pre-quantis
 D'Agostino scores with the kurtosis and power they come from, and the bandpass state after the last segment -- plus a
 few hundred bytes / floats in clear so that a mismatch can be located.
 
-Why: K2..K5 and K7..K11 have no reference-held vector (pb_kernels.cu cannot be built here), so the oracle is the only
-statement of those kernels; the HIP kernels are tested against it bit for bit, and nothing else would notice if oracle
-and kernels drifted TOGETHER.  With this fixture any change to pb_oracle.c's arithmetic turns
+Why: K2..K5 and K7..K11 have no reference-held vector; the HIP kernels are tested against the oracle bit for bit, and
+without a GPU nothing else would notice if oracle and kernels drifted TOGETHER (on the GPU the reference's own kernel
+file, compiled for gfx950, is run against the oracle: tests/test_gpu_ref_kernels.py).  With this fixture any change to pb_oracle.c's arithmetic turns
 tests/test_oracle_kchain.py red; regenerate (python tests/golden/make_kchain_golden.py) only in the same commit as the
 change, with the reason in the commit message.
 

@@ -36,6 +36,7 @@ def test_coadd_tree_every_leaf_count_is_the_defined_order():
             pl = _planes(N, nfloat, 100 + N)
             d = [torch.from_numpy(p).to(dev) for p in pl]
             dst = torch.full((nfloat,), float("nan"), dtype=torch.float32, device=dev)
+            torch.cuda.synchronize()        # the fill runs on torch's stream, the sum on the handle's non-blocking one
             order = coadd.tree_order(range(N))
             h.coadd_tree([d[a].data_ptr() for a in order], dst.data_ptr(), nfloat)
             h.sync()
@@ -93,6 +94,7 @@ def test_coadd_local_tree_over_a_handles_antennas(A):
         planes = [h.fetch(a, 0, S, raw=False, kur=False, ave=True)["ave_kur"] for a in range(A)]
         n = S * h.ave_per_seg
         dst = torch.full((n,), float("nan"), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()            # as above: the NaN fill must have landed before the handle's stream writes
         h.coadd_local_tree(S, coadd.tree_order(range(A)), dst.data_ptr())
         h.sync()
         torch.cuda.synchronize()
