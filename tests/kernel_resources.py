@@ -27,3 +27,9 @@ def compile_usage(src):
         if m and cur:
             use.setdefault(cur, {})[m.group(1)] = int(m.group(2))
     return use, asm
+
+
+def kernel_text(asm, sym):
+    """the instructions of the kernel whose symbol is sym: from its label to the end of its function"""
+    start = asm.index("\n%s:" % sym)
+    return asm[start:asm.index(".Lfunc_end", start)]

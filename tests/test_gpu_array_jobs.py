@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import beamproj_ref as PR
 from helpers import libpb, make_input
 
 pytestmark = pytest.mark.gpu
@@ -48,10 +49,13 @@ def _calls():
     psi5 = rng.uniform(-1.0, 1.0, (5, A))
     g5 = rng.uniform(0.5, 1.5, (5, A)).astype(np.float32)
     row0 = rng.integers(0, T - 5 + 1, (3, NCO)).astype(np.int32)
+    p1, p5 = PR.random_proj(A, 6), PR.random_proj(A, 7)
     return [("beam 1 x tscr 4", lambda h: h.beamform(0, S, d1, tscr=4)),
             ("corr int_rows 8", lambda h: h.correlate(0, S, 8)),
+            ("proj 1 x tscr 4", lambda h: h.beamform_proj(0, S, d1, p1, tscr=4)),
             ("beam 5 x tscr 1", lambda h: h.beamform(1, S, d5, psi5, g5, tscr=1)),
             ("corr int_rows 2", lambda h: h.correlate(1, S, 2)),
+            ("proj 5 x tscr 1", lambda h: h.beamform_proj(1, S, d5, p5, psi5, g5, tscr=1)),
             ("gated raw", lambda h: h.correlate_gated(0, S, row0, 5)),
             ("gated kur", lambda h: h.correlate_gated(1, S, row0, 5))]
 
@@ -65,10 +69,10 @@ def test_growth_keeps_nothing_stale():
     calls = _calls()
     with _fed(lp) as h:
         got = [f(h) for _, f in calls]
-    assert got[0][0].shape == (1, 4, 4, NCO) and got[2][0].shape == (5, 16, 4, NCO)
-    assert got[1][0].shape == (2, 3, 4, NCO) and got[3][0].shape == (8, 3, 4, NCO) and got[4][0].shape == (3, 3, 4, NCO)
+    assert got[0][0].shape == got[2][0].shape == (1, 4, 4, NCO) and got[3][0].shape == got[5][0].shape == (5, 16, 4, NCO)
+    assert got[1][0].shape == (2, 3, 4, NCO) and got[4][0].shape == (8, 3, 4, NCO) and got[6][0].shape == (3, 3, 4, NCO)
     # the seeded bytes hold flagged rows: the excised stream's counts differ from the raw stream's
-    assert got[3][1].min() < 2 and got[1][1].min() == 8
+    assert got[4][1].min() < 2 and got[1][1].min() == 8
     for (name, f), g in zip(calls, got):
         with _fed(lp) as fresh:
             ref = f(fresh)
@@ -77,7 +81,7 @@ def test_growth_keeps_nothing_stale():
             assert np.array_equal(_bits(x), _bits(y)), name
 
 
-@pytest.mark.parametrize("small,large", [(1, 3), (0, 2)], ids=["correlate", "beamform"])
+@pytest.mark.parametrize("small,large", [(1, 4), (0, 3), (2, 5)], ids=["correlate", "beamform", "beamform_proj"])
 def test_device_bytes_follow_the_buffers(small, large):
     lp = libpb()
     calls = _calls()
@@ -98,13 +102,16 @@ def test_timers():
     calls = _calls()
     with _fed(lp) as h:
         assert h.correlate_timers() == (0.0, 0.0) and h.beamform_timers() == (0.0, 0.0, 0.0)
+        assert h.beamform_proj_timers() == (0.0, 0.0, 0.0)
         calls[1][1](h)
         assert h.beamform_timers() == (0.0, 0.0, 0.0)
         calls[0][1](h)
-        ct, bt = h.correlate_timers(), h.beamform_timers()
-    assert len(ct) == 2 and len(bt) == 3
-    assert all(np.isfinite(v) and v >= 0 for v in ct + bt), (ct, bt)
-    assert ct[0] > 0 and bt[1] > 0, (ct, bt)                        # the kernel stages
+        assert h.beamform_proj_timers() == (0.0, 0.0, 0.0)          # a plain call leaves the projecting call's alone
+        calls[2][1](h)
+        ct, bt, pt = h.correlate_timers(), h.beamform_timers(), h.beamform_proj_timers()
+    assert len(ct) == 2 and len(bt) == 3 and len(pt) == 3
+    assert all(np.isfinite(v) and v >= 0 for v in ct + bt + pt), (ct, bt, pt)
+    assert ct[0] > 0 and bt[1] > 0 and pt[1] > 0, (ct, bt, pt)      # the kernel stages
 
 
 def test_which_refusal_wins():

@@ -124,8 +124,7 @@ struct pb_handle {
     hipStream_t s_coadd = nullptr;   // stream of pb_coadd_local / pb_coadd_finish (nullptr: the main stream)
     int coadd_slot = 0, coadd_last = 0;
     struct pb_corr_state *corr = nullptr;   // the correlator's job (pb_job.h; pb_correlate.hip), from its first call on
-    struct pb_beam_state *beam = nullptr;   // the beamformer's (pb_beamform.hip), likewise
-    struct pb_beamproj_state *beamproj = nullptr;   // the projecting beamformer's (pb_beamproj.hip), likewise
+    struct pb_beam_state *beam = nullptr, *beamproj = nullptr;   // pb_beamform's and pb_beamform_proj's (pb_beamform.hip), likewise
     FftTables ft = {};
     DagConsts dag = {}, dag_fb = {};   // D'Agostino constants for N = 500 (blocks) and N = 12500 (FFT rows, K4)
     int dag_bands = 0;               // 1: crossings located (flags decided without the cube root); -1: PB_DAG_BANDS=0; -2: search failed, fallback
@@ -163,8 +162,7 @@ struct StreamScope {
 PB_LOCAL int fail(pb_handle *h, int code, const std::string &msg);   // h = nullptr: the error pb_create reports
 PB_LOCAL hipError_t sync_all(pb_handle *h);
 PB_LOCAL void pb_correlate_free(pb_handle *h);                       // pb_correlate.hip: what pb_destroy releases
-PB_LOCAL void pb_beamform_free(pb_handle *h);                        // pb_beamform.hip: likewise
-PB_LOCAL void pb_beamproj_free(pb_handle *h);                        // pb_beamproj.hip: likewise
+PB_LOCAL void pb_beamform_free(pb_handle *h);                        // pb_beamform.hip: likewise, both calls' states
 
 template <class T>
 static hipError_t dmalloc(pb_handle *h, T **p, size_t n)

@@ -1,5 +1,5 @@
 // The rotation polynomial of include/pb_hip.h (the imager's block), shared by the imager (pb_image.hip) and the
-// beamformer (pb_beamform.hip).
+// beamformer's steering weight (pb_beamform.hip: beam_steer, for both of its calls).
 #pragma once
 #include <hip/hip_runtime.h>
 
