@@ -458,6 +458,53 @@ int pb_beamform_proj(pb_handle *h, int stream, int nseg, int nbeam, const double
                      float *beams, int32_t *rows_used);
 int pb_beamform_proj_timers(const pb_handle *h, float *ms3);
 
+/* ---- beam planes: the beams as filterbank planes that stay on the device, ready for pb_search_push_f32 (reference:
+ * the filterbank's own fp32 plane is pow / bandpass - 1 scaled to unit variance, src/pb_kernels.cu
+ * detect_and_normalize3, and the search quantises such a plane with the 8-bit rule; the rest is THIS project's own;
+ * tests/beam_plane_ref.py restates it).
+ * Definition, operation by operation.  Every line is one binary32 operation unless marked binary64; none is contracted
+ * with another.
+ *   inputs     out[b][s][q][c]: pb_beamform's block for the same arguments, bit for bit; with a non-NULL proj,
+ *              pb_beamform_proj's.  used[b][s][c]: that call's rows_used (tscr on the raw stream, the respective call's
+ *              count on the excised stream).  Neither leaves the device.
+ *   power      per (b, s, c):   I = AA + BB      ratio = (float)tscr / (float)used      J = I * ratio
+ *              At used == tscr the ratio is 1 and J = I exactly.  At used == 0 the sample has no J.
+ *   level      L[b][c].  Output samples are taken in chunks of 32 consecutive s (the last chunk may be short).  Within a
+ *              chunk a binary64 sum, starting from 0.0, adds (double)J in ascending s over the samples with used > 0; the
+ *              chunk sums are then added in binary64, starting from 0.0, in ascending chunk order.  With n the number of
+ *              samples with used > 0:
+ *                  L = n > 0 ? (float)(sum / (double)n) : 0.0f               (the division in binary64)
+ *              No atomics: the order is the definition and depends on neither nbeam nor the launch.
+ *   plane      Le = level_in ? level_in[b][c] : L           g = sqrtf((float)(2 * tscr))
+ *                  plane[b][s][c] = (used > 0 && Le > 0) ? (J / Le - 1.0f) * g : +0.0f
+ *              (a division, a subtraction, a multiplication).  AA + BB over tscr rows of Gaussian voltages has
+ *              std / mean = 1 / sqrt(2 tscr), so a noise plane has zero mean and unit variance: the convention of the
+ *              filterbank's fp32 plane, which pb_search_push_f32 quantises with scale = 1.  The quantiser saturates at
+ *              3.77 sigma, so nothing is clipped here; a sample without a valid row sits on the mean.
+ * level_in   host float32 [nbeam][4096] or NULL: a level of the caller's, e.g. a running mean of earlier calls' level_out,
+ *            so that batches share one scale.
+ * Outputs: level_out host float32 [nbeam][4096] or NULL: L, whether or not level_in is given; planes host float32
+ * [nbeam][nout][4096] or NULL; *d_planes (d_planes may be NULL): the device address of [nbeam][nout][4096] float32,
+ * 16-byte aligned, as every beam's block in it is, valid until the next pb_beamform / pb_beamform_proj / pb_beam_planes
+ * call on the handle or pb_destroy.
+ *   pb_beam_planes         runs as pb_beamform does: on the SELECTED set, on the beam call's stream behind that set's
+ *                          channeliser and detect.  The four-product block and the row counts are never copied.  It
+ *                          returns with its stream drained, so the planes at *d_planes are complete: the caller meets
+ *                          pb_search_push_f32's contract that the producer is synchronised.  The library owns and grows
+ *                          the buffers (pb_beamform's, or pb_beamform_proj's with a proj, and the planes, levels and
+ *                          chunk sums) and frees them in pb_destroy; pb_query's device_bytes follows them.  No other
+ *                          state of the handle changes: pb_fetch, pb_beamform, pb_beamform_proj and their timers return
+ *                          what they returned before.
+ *   pb_beam_planes_timers  device time of the last call in ms: the uploads, weights and row counts; the beam kernel; the
+ *                          level and plane kernels; the copies to the host.
+ * Refused, with a pb_last_error text under this call's name, on the host before anything is queued: everything
+ * pb_beamform refuses; with a non-NULL proj everything pb_beamform_proj refuses; PB_EINVAL for a level_in value that is
+ * not finite or is negative. */
+int pb_beam_planes(pb_handle *h, int stream, int nseg, int nbeam, const double *delay, const double *psi,
+                   const float *gain, const float *proj, const int32_t *shift, int tscr, int nout,
+                   const float *level_in, float *level_out, float *planes, const float **d_planes);
+int pb_beam_planes_timers(const pb_handle *h, float *ms4);
+
 int pb_profile(pb_handle *h, int enable);
 int pb_get_timers(pb_handle *h, pb_timers *out, int reset);
 int pb_debug_fetch(pb_handle *h, int what, int ant, int seg, void *dst, size_t nbytes);

@@ -20,7 +20,8 @@ Only the hot path of the reference's process_baseband executable lives here:
   triggers.py      trigger_t wire format towards the voltage dumper
   correlate.py     visibilities and lag delays of a set of antennas' voltage dumps (pb_correlate*)
   localise.py      fine delays and a sky position from those visibilities (pb_imager_*)
-  beamform.py      coherent beams of those antennas at such delays, beside their incoherent sum (pb_beamform)
+  beamform.py      coherent beams of those antennas at such delays, beside their incoherent sum (pb_beamform); --search / --fil: the
+                   beams as planes that stay on the GPU, searched there and written as .fil (pb_beam_planes)
   nulling.py       per-pol, per-channel projectors that take interferers out of those beams (pb_beamform_proj)
   replay_batches.py  what those two tools share: their common arguments, the dump reader, the batch loop over a handle
 """

@@ -13,7 +13,7 @@ Command line (offline; the dump files are those the hosts' --replay reads, read 
   python -m vlite-fast_amd.beamform --replay ant0.uw ant1.uw ... [--offsets n0 n1 ...] [--stream raw|kur]
          (--delays d0 d1 ... | --beams beams.txt | --loc loc.npz) [--phase-turns] [--dm DM] [--tscr N]
          [--rows-per-seg N] [--max-seg N] [--seconds N] [--null K [--null-min-ratio X] [--null-train ROW0 ROW1]]
-         -o beams.npz
+         [--search "<search flags>" [--search-single]] [--fil DIR] [--level-alpha X] -o beams.npz
   (--rows-per-seg R --max-seg S: the handle's batch, 1024 x 10 rows = one second by default; a file's tail that does not
   fill a batch is left out.  Per batch the tool emits the output samples whose whole window -- in every channel, with
   the shift of --dm -- lies within the batch: the correlate tool's limit for its gates, and an output sample is never
@@ -36,13 +36,34 @@ projectors (with --null-min-ratio X only in channels whose largest eigenvalue is
 others) and forms the coherent beams with pb_beamform_proj.  The single-antenna beams stay un-nulled, through
 pb_beamform, so `incoherent` and `ratio` mean what they mean without --null.
 
+--search "<flags>" searches every coherent beam for pulses where it lies on the GPU: per batch
+pb_beam_planes turns the beams into zero-mean, unit-variance fp32 planes that stay in HBM, and each beam's plane is fed to
+a search of its own (search.parse_flags and search.open_search, as process_baseband --search does; GulpSearch.feed_plane
+quantises it to 8 bits with the reference's rule).  The flags are the search tool's less -f and -stream_chunk; -beam is set
+by this tool: coherent beam b is beam b + 1, and with --search-single the nant single-antenna beams follow as beams
+nbeam + 1 .. nbeam + nant (un-nulled, like `incoherent`).  The band in the search's header is the filterbank's own fch1 and
+foff: plane channel c is FFT bin 2155 + c, the filterbank's channel c (tests/test_gpu_beam_planes.py holds the two planes
+to each other), and tsamp = tscr * 12500 / 128e6 s.  The search dedisperses itself and the batches must tile time, so
+--search refuses --dm and a --tscr that does not divide a batch's rows.  One searcher at the production flags holds
+2.17 GB of device memory, which bounds the beams one card can search.
+--fil DIR writes each searched beam's 8-bit SIGPROC filterbank, DIR/beamNN.fil: the bytes are those the search's quantiser
+makes of the plane on the device (Searcher.push_plane into a searcher kept for that purpose, fetched and transposed); the
+host has no quantiser of its own.  sigproc.sigproc_header writes the filterbank's 781.25 us sampling only, so --fil is
+accepted at --tscr 8 alone.
+The planes' level is a running one, kept on the host per (beam, channel): the first batch is divided by its own mean
+(pb_beam_planes' level_out), later batches by run, updated as run += alpha * (level_out - run) where level_out > 0 (a
+channel whose run is still 0 takes level_out as it is).  --level-alpha (default 0.25) is a host-side choice of this tool,
+not tuned and not part of the library's definition.
+
 beams.npz: beams float32 [nbeam][nout][4][4096] (the coherent beams' AA, BB, CR, CI dynamic spectra, tscr rows per
 sample), sample_row int64 [nout] (the first row, counted from the start of the data, of each output sample in channel
 0; channel c starts shift[c] rows later), shift int32 [4096], rows_used int32 [nbeam][nout][4096], incoherent float64
 [nout][4][4096] (the single-antenna beams added), series float64 [nbeam][nout] and incoherent_series float64 [nout]
 (AA + BB added over the band), ratio float64 [nbeam] (sum of series / sum of incoherent_series), delays float64
 [nbeam][nant], phase_turns float64 [nbeam][nant] (the psi handed to pb_beamform, in turns: -localise.phase_turns(delays)
-with --phase-turns, else 0), freqs_mhz [4096], tscr, options (JSON).  With --null also null_count int64 [2][4096], the vectors nulled per (pol,
+with --phase-turns, else 0), freqs_mhz [4096], tscr, options (JSON).  With --search also search_cands float64 [n][6]: beam number, S/N, peak sample
+(counted from the start of the data, in output samples), log2 boxcar width, trial-DM index, DM of every candidate, in the
+order the searches gave them.  With --null also null_count int64 [2][4096], the vectors nulled per (pol,
 channel), added over the batches, and rows_used counts every antenna (pb_beamform_proj's).
 """
 import argparse
@@ -100,6 +121,74 @@ def ratio(series, incoherent_series):
 # ---------------------------------------------------------------------------------------------------------------
 # the tool (its common arguments, the dump reader and the batch loop are shared with correlate.py: replay_batches.py)
 
+def update_level(run, level_out, alpha):
+    """the running level float32 [nbeam][4096] after a batch whose own level is level_out: level_out itself for the first
+    batch (run None) and where run is still 0, else run + alpha * (level_out - run) where level_out > 0"""
+    level_out = np.asarray(level_out, np.float32)
+    if run is None:
+        return level_out.copy()
+    step = (run + np.float32(alpha) * (level_out - run)).astype(np.float32)
+    return np.where(level_out > 0, np.where(run > 0, step, level_out), run).astype(np.float32)
+
+
+def plane_header(tscr):
+    """the SIGPROC fields that describe a beam plane: channel c is FFT bin 2155 + c -- the filterbank's own channel
+    order, so its fch1 and foff --, sampled every tscr rows"""
+    search = importlib.import_module("vlite-fast_amd.search")
+    return dict(nchans=NCHANOUT, fch1=search.FCH1, foff=search.FOFF, tsamp=tscr * 12500 / 128e6, tstart=40587.0, nbits=8, nifs=1)
+
+
+class PlaneSearch(object):
+    """What --search and --fil do with a group of beams that one pb_beam_planes call forms: the running level, one
+    GulpSearch per beam (--search) and one .fil file per beam (--fil), beam numbers first + 1 .. first + nbeam."""
+
+    def __init__(self, args, nbeam, first, quantiser):
+        self.nbeam, self.first, self.alpha, self.run = nbeam, first, args.level_alpha, None
+        self.searches, self.files, self.quantiser, self.cands = [], [], quantiser, []
+        if args.search is not None:
+            import copy
+            search = importlib.import_module("vlite-fast_amd.search")
+            for b in range(nbeam):
+                flags = copy.copy(args.search_flags)
+                flags.beam = first + b + 1
+                self.searches.append(search.open_search(flags, plane_header(args.tscr), flags.nsamps_gulp, device=args.device))
+        if args.fil is not None:
+            import os
+            sigproc = importlib.import_module("vlite-fast_amd.sigproc")
+            os.makedirs(args.fil, exist_ok=True)
+            for b in range(nbeam):
+                f = open(os.path.join(args.fil, "beam%02d.fil" % (first + b + 1)), "wb")
+                f.write(sigproc.sigproc_header(0, 0.0, 0.0, "beam%02d" % (first + b + 1), 40587.0, 1, 8))
+                self.files.append(f)
+
+    def _took(self, b, batch, emit):
+        emit(batch)
+        self.cands += [(self.first + b + 1, c["snr"], c["peak_idx"], c["tfilt"], c["dmi"], c["dm"]) for c in batch if "band" not in c]
+
+    def batch(self, h, stream, nseg, delay, psi, gain, proj, tscr, nout):
+        """form the group's planes for the handle's current batch (shifts 0) and hand each beam's on, where it lies"""
+        _, ptr, level_out = h.beam_planes(stream, nseg, delay, psi, gain, proj, None, tscr, nout, level=self.run, to_host=False)
+        self.run = update_level(self.run, level_out, self.alpha)
+        for b in range(self.nbeam):
+            at = ptr + b * nout * NCHANOUT * 4
+            if self.searches:
+                _, g, emit = self.searches[b]
+                self._took(b, g.feed_plane(device_ptr=at, nsamp=nout, scale=1.0), emit)
+            if self.files:
+                q = self.quantiser
+                q.push_plane(device_ptr=at, nsamp=nout, scale=1.0)
+                self.files[b].write(np.ascontiguousarray(q.gulp_fetch().T).tobytes())
+                q.gulp_advance(0)
+
+    def close(self):
+        for b, (s, g, emit) in enumerate(self.searches):
+            self._took(b, g.flush(), emit)
+            self._took(b, g.finish(), emit)
+            s.close()
+        for f in self.files:
+            f.close()
+
+
 def make_parser():
     p = argparse.ArgumentParser(prog="beamform", description="coherent beams from voltage dumps")
     replay_batches.add_arguments(p)
@@ -117,6 +206,12 @@ def make_parser():
                    help="null only where the largest eigenvalue is at least X times the mean of the others")
     p.add_argument("--null-train", nargs=2, type=int, default=None, metavar=("ROW0", "ROW1"),
                    help="rows ROW0 .. ROW1 - 1 of each batch make the matrices (default: all)")
+    p.add_argument("--search", default=None, metavar="FLAGS",
+                   help="search every coherent beam on the GPU: the search tool's flags in one string (-beam is set here)")
+    p.add_argument("--search-single", action="store_true", help="with --search or --fil: the single-antenna beams too")
+    p.add_argument("--fil", default=None, metavar="DIR", help="write each searched beam's 8-bit filterbank to DIR/beamNN.fil (--tscr 8)")
+    p.add_argument("--level-alpha", type=float, default=0.25,
+                   help="weight of a batch's own level in the planes' running level (a host-side choice, not tuned)")
     return p
 
 
@@ -140,6 +235,21 @@ def parse_args(argv=None):
         p.error("--null-min-ratio must be positive")
     if a.null_train is not None and not 0 <= a.null_train[0] < a.null_train[1] <= a.rows_per_seg * a.max_seg:
         p.error("--null-train: 0 <= ROW0 < ROW1 <= the %d rows of a batch" % (a.rows_per_seg * a.max_seg))
+    a.search_flags = None
+    if a.search is not None or a.fil is not None:
+        if a.dm is not None:
+            p.error("--search and --fil: not with --dm (the search dedisperses itself, and the shifts must be 0 so that batches tile time)")
+        if (a.rows_per_seg * a.max_seg) % a.tscr:
+            p.error("--search and --fil: --tscr must divide the %d rows of a batch" % (a.rows_per_seg * a.max_seg))
+        if not 0 < a.level_alpha <= 1:
+            p.error("--level-alpha must be in (0, 1]")
+    elif a.search_single:
+        p.error("--search-single needs --search or --fil")
+    if a.fil is not None and a.tscr != 8:
+        p.error("--fil: only at --tscr 8: the SIGPROC header this project writes (sigproc.sigproc_header) carries the "
+                "filterbank's own sampling of 8 rows, 781.25 us, and no other")
+    if a.search is not None:
+        a.search_flags = importlib.import_module("vlite-fast_amd.search").parse_flags(a.search)
     return a
 
 
@@ -183,7 +293,18 @@ def run(args):
     beams, used, incoherent, rows = [], [], [], []
     nulling = importlib.import_module("vlite-fast_amd.nulling") if args.null is not None else None
     null_count = np.zeros((2, NCHANOUT), np.int64)
+    # --search / --fil: the coherent beams' planes, and with --search-single the single-antenna beams' (un-nulled)
+    planes = args.search is not None or args.fil is not None
+    coherent = single = quantiser = None
     for k, h, stream in replay_batches.batches(args, "beamform"):
+        if planes and coherent is None:
+            if args.fil is not None:
+                searcher = importlib.import_module("vlite-fast_amd.searcher")
+                quantiser = searcher.Searcher(device=args.device, nchan=NCHANOUT, max_samples=nout + 128, dm_min=0, dm_max=1,
+                                              dm_step=1, boxcar_max=1, zap=())
+                quantiser.set_gulp(1)
+            coherent = PlaneSearch(args, nb, 0, quantiser)
+            single = PlaneSearch(args, nant, nb, quantiser) if args.search_single else None
         if nulling is None:
             v, u = h.beamform(stream, S, all_delay, all_psi, all_gain, shift, tscr, nout)
             beams.append(v[:nb].copy())
@@ -199,6 +320,17 @@ def run(args):
             used.append(u)
             incoherent.append(h.beamform(stream, S, d1, None, g1, shift, tscr, nout)[0].astype(np.float64).sum(axis=0))
         rows.append(k * T + tscr * np.arange(nout, dtype=np.int64))
+        if planes:                                              # (last: the planes live until the handle's next beam call)
+            coherent.batch(h, stream, S, delay, psi, None, proj if nulling is not None else None, tscr, nout)
+            if single is not None:
+                single.batch(h, stream, S, d1, None, g1, None, tscr, nout)
+    cands = []
+    for group in (coherent, single):
+        if group is not None:
+            group.close()
+            cands += group.cands
+    if quantiser is not None:
+        quantiser.close()
     beams = np.concatenate(beams, axis=1)
     incoherent = np.concatenate(incoherent, axis=0)
     series = beams[:, :, :2].astype(np.float64).sum(axis=(2, 3))
@@ -208,7 +340,13 @@ def run(args):
                rows_used=np.concatenate(used, axis=1), incoherent=incoherent, series=series, incoherent_series=inc_series,
                ratio=ratio(series, inc_series), delays=delay, phase_turns=np.zeros_like(delay) if psi is None else psi,
                freqs_mhz=corr.chan_freqs_mhz(), tscr=np.int64(tscr))
+    if args.search is not None:
+        out["search_cands"] = np.array(cands, np.float64).reshape(len(cands), 6)
     options = vars(args).copy()
+    del options["search_flags"]
+    if not planes:
+        for name in ("search", "search_single", "fil", "level_alpha"):      # without them the file is what it was
+            del options[name]
     if nulling is None:
         for name in ("null", "null_min_ratio", "null_train"):       # without --null the file is what it was
             del options[name]

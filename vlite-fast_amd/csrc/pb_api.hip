@@ -481,6 +481,7 @@ extern "C" void pb_destroy(pb_handle *h)
     if (h->s_copy) (void)hipStreamSynchronize(h->s_copy);
     pb_correlate_free(h);
     pb_beamform_free(h);
+    pb_beam_plane_free(h);
     for (auto &kv : h->plans) hipfftDestroy(kv.second);
     for (auto &b : h->sets) {    // (a set pb_create did not finish: what it never allocated is null)
         void *sp[] = {b.d_in, b.d_flags, b.d_codes, b.d_wrow, b.d_stats, b.d_fraw, b.d_fkur,

@@ -34,60 +34,16 @@
 //   (amdgpu_waves_per_eu), which at eight antennas makes the compiler fit 250 VGPRs where it otherwise took 256 and 4
 //   AGPRs and one wave (sixteen beams: 3.42 ms).  No LDS, no atomics, no scratch.
 // Host side: pb_beam_state is a job of csrc/pb_job.h (stream, stage events and times, owned buffers that grow, teardown);
-// a handle keeps one for each of the two calls, and beam_call is the host path of both.  What the call refuses about the
-// handle, the stream and the batch is that header's spectra_check_*.
-#include "pb_job.h"
+// a handle keeps one for each of the two calls, and beam_call is the host path of both: beam_check (the refusals) and
+// beam_queue (uploads, weights, row counts, beam kernel), which pb_beam_planes (pb_beam_plane.hip) runs too, then the
+// copies to the host.  What the call refuses about the handle, the stream and the batch is that header's spectra_check_*.
+#include "pb_beam.h"      // the call's state, the kernels' arguments, and what pb_beam_plane.hip shares of the host path
 #include "rotation_dev.h"
 
 #include <vector>
 
-#define BEAM_MAX_BEAMS 64
 #define BEAM_TILE 4             // beams of a workgroup
 #define BEAM_CHUNK_ROWS 32      // rows of a workgroup's run: max(1, BEAM_CHUNK_ROWS / tscr) output samples
-
-struct BeamArgs {
-    const float2 *X;       // one stream's spectra [A][S][2][R][4096]
-    const float2 *W;       // [nbeam][A][4096] weights; projecting: [nbeam][2][A][4096]
-    const int32_t *shift;  // [4096] first row of output sample 0 per channel
-    const int32_t *pref;   // [nbeam][T + 1] rows before t that count for the beam (projecting: [T + 1]); nullptr on the raw stream
-    float *beams;          // [nbeam][nout][4][4096]
-    int32_t *used;         // [nbeam][nout][4096]
-    int S, R, T, nbeam, tscr, nout, spc;   // spc: output samples per workgroup
-};
-
-// pinned host memory that is freed with the struct it is a member of: the matrices go to the device from here, so that
-// their upload is a DMA transfer that does not wait for the host
-struct PB_LOCAL PinnedProj {
-    float2 *p = nullptr;
-    size_t cap = 0;      // elements
-    PinnedProj() = default;
-    PinnedProj(PinnedProj &&) = delete;
-    ~PinnedProj() { if (p) (void)hipHostFree(p); }
-    hipError_t grow(size_t n)
-    {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipHostMalloc((void **)&p, n * sizeof(float2), hipHostMallocDefault);
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-};
-
-struct PB_LOCAL pb_beam_state : PbJob<3> {      // stages: uploads + weights + row counts, beam kernel, copy to the host
-    DevBuf<double> par;                  // [2][BEAM_MAX_BEAMS * PB_SPECTRA_MAX_ANT]: delay / 12500, psi
-    DevBuf<float> gain;                  // [BEAM_MAX_BEAMS * PB_SPECTRA_MAX_ANT]
-    DevBuf<int32_t> shift;               // [4096]
-    DevBuf<float2> proj;                 // [2][A][A][4096]; empty for the plain call, as h_proj is
-    DevBuf<float2> W;
-    DevBuf<float> beams;
-    DevBuf<int32_t> used, pref;
-    std::vector<double> h_par;
-    std::vector<float> h_gain;
-    std::vector<int32_t> h_shift;
-    PinnedProj h_proj;                   // [2][A][A][4096], the device's layout
-};
 
 typedef float beam_pair __attribute__((ext_vector_type(2)));      // one value for each of two beams
 
@@ -357,48 +313,55 @@ void pb_beamform_free(pb_handle *h)
     job_free(h->beamproj);
 }
 
-// Both calls, under the name w, on the call's own state bs.  The plain call has no matrices to check, stage or upload,
-// one set of weights per beam and a row count per beam; past the refusals, proj != nullptr is the projecting call.
-static int beam_call(pb_handle *h, const std::string &w, pb_beam_state *&bs, bool projecting, int stream, int nseg, int nbeam,
-                     const double *delay, const double *psi, const float *gain, const float *proj, const int32_t *shift,
-                     int tscr, int nout, float *beams, int32_t *rows_used)
+// What both calls refuse, under the name w: everything refused is refused here, on the host, before anything is queued.
+// The plain call has no matrices to check; past the refusals, c.proj != nullptr is the projecting call.
+int beam_check(pb_handle *h, const std::string &w, bool projecting, BeamCall &c)
 {
-    // everything refused is refused here, on the host, before anything is queued
-    if (int rc = spectra_check_config(h, w, stream, nseg)) return rc;
-    if (tscr < 1 || nout < 1) return fail(h, PB_EINVAL, w + ": tscr and nout must be positive");
-    if (nbeam < 1 || nbeam > BEAM_MAX_BEAMS) return fail(h, PB_EINVAL, w + ": nbeam must be 1..64");
-    const size_t nused = (size_t)nbeam * nout * PB_NCHANOUT, nval = nused * 4;
-    if (!job_output_fits(nval * sizeof(float))) return fail(h, PB_EINVAL, w + ": outputs beyond 2 GiB; use fewer beams or samples per call");
-    if (!delay) return fail(h, PB_EINVAL, w + ": delay is null");
-    if (projecting && !proj) return fail(h, PB_EINVAL, w + ": proj is null");
-    const int A = h->A, n = nbeam * A;
+    if (int rc = spectra_check_config(h, w, c.stream, c.nseg)) return rc;
+    if (c.tscr < 1 || c.nout < 1) return fail(h, PB_EINVAL, w + ": tscr and nout must be positive");
+    if (c.nbeam < 1 || c.nbeam > BEAM_MAX_BEAMS) return fail(h, PB_EINVAL, w + ": nbeam must be 1..64");
+    c.nused = (size_t)c.nbeam * c.nout * PB_NCHANOUT;
+    c.nval = c.nused * 4;
+    if (!job_output_fits(c.nval * sizeof(float))) return fail(h, PB_EINVAL, w + ": outputs beyond 2 GiB; use fewer beams or samples per call");
+    if (!c.delay) return fail(h, PB_EINVAL, w + ": delay is null");
+    if (projecting && !c.proj) return fail(h, PB_EINVAL, w + ": proj is null");
+    const int A = h->A, n = c.nbeam * A;
     for (int k = 0; k < n; ++k) {
-        if (!delay_ok(delay[k])) return fail(h, PB_EINVAL, w + ": a delay is not finite or beyond 2^24 samples");
-        if (psi && !std::isfinite(psi[k])) return fail(h, PB_EINVAL, w + ": a psi is not finite");
-        if (gain && !std::isfinite(gain[k])) return fail(h, PB_EINVAL, w + ": a gain is not finite");
+        if (!delay_ok(c.delay[k])) return fail(h, PB_EINVAL, w + ": a delay is not finite or beyond 2^24 samples");
+        if (c.psi && !std::isfinite(c.psi[k])) return fail(h, PB_EINVAL, w + ": a psi is not finite");
+        if (c.gain && !std::isfinite(c.gain[k])) return fail(h, PB_EINVAL, w + ": a gain is not finite");
     }
     int max_shift = 0;
-    if (shift)
-        for (int c = 0; c < PB_NCHANOUT; ++c) {
-            if (shift[c] < 0) return fail(h, PB_EINVAL, w + ": a shift is negative");
-            if (shift[c] > max_shift) max_shift = shift[c];
+    if (c.shift)
+        for (int k = 0; k < PB_NCHANOUT; ++k) {
+            if (c.shift[k] < 0) return fail(h, PB_EINVAL, w + ": a shift is negative");
+            if (c.shift[k] > max_shift) max_shift = c.shift[k];
         }
-    const size_t nproj = proj ? (size_t)2 * A * A * PB_NCHANOUT : 0;
-    for (size_t k = 0; k < 2 * nproj; ++k)
-        if (!std::isfinite(proj[k])) return fail(h, PB_EINVAL, w + ": a proj value is not finite");
-    if (int rc = spectra_check_batch(h, w, nseg)) return rc;
-    const int T = nseg * h->R;
-    if ((int64_t)max_shift + (int64_t)nout * tscr > T) return fail(h, PB_EINVAL, w + ": a window leaves the batch's rows");
+    c.nproj = c.proj ? (size_t)2 * A * A * PB_NCHANOUT : 0;
+    for (size_t k = 0; k < 2 * c.nproj; ++k)
+        if (!std::isfinite(c.proj[k])) return fail(h, PB_EINVAL, w + ": a proj value is not finite");
+    if (int rc = spectra_check_batch(h, w, c.nseg)) return rc;
+    c.T = c.nseg * h->R;
+    if ((int64_t)max_shift + (int64_t)c.nout * c.tscr > c.T) return fail(h, PB_EINVAL, w + ": a window leaves the batch's rows");
+    return PB_OK;
+}
 
+// The first part of a checked call, on the call's own state bs: stage, upload, weights, row counts and the beam kernel.
+// The plain call has no matrices to stage or upload, one set of weights per beam and a row count per beam.
+int beam_queue(pb_handle *h, pb_beam_state *&bs, const BeamCall &c, bool want_beams, bool want_used, const BeamUpload *more)
+{
+    const int A = h->A, nbeam = c.nbeam, n = nbeam * A, T = c.T;
+    const float *proj = c.proj;
+    const size_t nproj = c.nproj;
     if (!bs) bs = new pb_beam_state;
     bs->h_par.resize(2 * (size_t)n);
     bs->h_gain.resize(n);
     for (int k = 0; k < n; ++k) {
-        bs->h_par[k] = delay_slope(delay[k]);
-        bs->h_par[n + k] = psi ? psi[k] : 0.0;
-        bs->h_gain[k] = gain ? gain[k] : 1.0f;
+        bs->h_par[k] = delay_slope(c.delay[k]);
+        bs->h_par[n + k] = c.psi ? c.psi[k] : 0.0;
+        bs->h_gain[k] = c.gain ? c.gain[k] : 1.0f;
     }
-    if (shift) bs->h_shift.assign(shift, shift + PB_NCHANOUT);
+    if (c.shift) bs->h_shift.assign(c.shift, c.shift + PB_NCHANOUT);
     else bs->h_shift.assign(PB_NCHANOUT, 0);
 
     HIPCHK(h, bs->ensure(h->cfg.device));
@@ -407,20 +370,20 @@ static int beam_call(pb_handle *h, const std::string &w, pb_beam_state *&bs, boo
         // finished: every call returns with its stream drained)
         HIPCHK(h, bs->h_proj.grow(nproj));
         for (int p = 0; p < 2; ++p)
-            for (int c = 0; c < PB_NCHANOUT; ++c) {
-                const float *src = proj + ((size_t)p * PB_NCHANOUT + c) * A * A * 2;
+            for (int k = 0; k < PB_NCHANOUT; ++k) {
+                const float *src = proj + ((size_t)p * PB_NCHANOUT + k) * A * A * 2;
                 for (int aj = 0; aj < A * A; ++aj)
-                    bs->h_proj.p[((size_t)p * A * A + aj) * PB_NCHANOUT + c] = make_float2(src[2 * aj], src[2 * aj + 1]);
+                    bs->h_proj.p[((size_t)p * A * A + aj) * PB_NCHANOUT + k] = make_float2(src[2 * aj], src[2 * aj + 1]);
             }
     }
-    const bool count = stream == PB_CORR_KUR && rows_used;      // rows_used of the excised stream: from the row counts
+    const bool count = c.stream == PB_CORR_KUR && want_used;      // rows_used of the excised stream: from the row counts
     HIPCHK(h, bs->par.grow(h, (size_t)2 * BEAM_MAX_BEAMS * PB_SPECTRA_MAX_ANT));
     HIPCHK(h, bs->gain.grow(h, (size_t)BEAM_MAX_BEAMS * PB_SPECTRA_MAX_ANT));
     HIPCHK(h, bs->shift.grow(h, (size_t)PB_NCHANOUT));
     if (proj) HIPCHK(h, bs->proj.grow(h, nproj));
     HIPCHK(h, bs->W.grow(h, (size_t)(proj ? 2 : 1) * n * PB_NCHANOUT));
-    if (beams) HIPCHK(h, bs->beams.grow(h, nval));
-    if (rows_used) HIPCHK(h, bs->used.grow(h, nused));
+    if (want_beams) HIPCHK(h, bs->beams.grow(h, c.nval));
+    if (want_used) HIPCHK(h, bs->used.grow(h, c.nused));
     if (count) HIPCHK(h, bs->pref.grow(h, (size_t)(proj ? 1 : nbeam) * (T + 1)));
 
     const pb_handle::BufSet &b = h->set();
@@ -432,30 +395,43 @@ static int beam_call(pb_handle *h, const std::string &w, pb_beam_state *&bs, boo
     HIPCHK(h, bs->gain.from_host(bs->h_gain.data(), (size_t)n, bs->st));
     HIPCHK(h, bs->shift.from_host(bs->h_shift.data(), PB_NCHANOUT, bs->st));
     if (proj) HIPCHK(h, bs->proj.from_host(bs->h_proj.p, nproj, bs->st));
+    if (more) HIPCHK(h, hipMemcpyAsync(more->dst, more->src, more->n * sizeof(float), hipMemcpyHostToDevice, bs->st));
     BeamArgs a;
-    a.X = (const float2 *)(stream == PB_CORR_KUR ? b.d_Pkur : b.d_Praw);
+    a.X = (const float2 *)(c.stream == PB_CORR_KUR ? b.d_Pkur : b.d_Praw);
     a.W = bs->W.p;
     a.shift = bs->shift.p;
     a.pref = count ? bs->pref.p : nullptr;
-    a.beams = beams ? bs->beams.p : nullptr;
-    a.used = rows_used ? bs->used.p : nullptr;
+    a.beams = want_beams ? bs->beams.p : nullptr;
+    a.used = want_used ? bs->used.p : nullptr;
     a.S = h->S;
     a.R = h->R;
     a.T = T;
     a.nbeam = nbeam;
-    a.tscr = tscr;
-    a.nout = nout;
-    a.spc = tscr >= BEAM_CHUNK_ROWS ? 1 : BEAM_CHUNK_ROWS / tscr;
+    a.tscr = c.tscr;
+    a.nout = c.nout;
+    a.spc = c.tscr >= BEAM_CHUNK_ROWS ? 1 : BEAM_CHUNK_ROWS / c.tscr;
     // the plain call's weights go before its row counts, the projecting call's after them
     if (!proj) k_beam_weights<<<dim3(PB_NCHANOUT / 64, n), 64, 0, bs->st>>>(bs->par.p, bs->par.p + n, bs->gain.p, bs->W.p);
     if (count)
         k_beam_prefix<<<proj ? 1 : nbeam, 64, 0, bs->st>>>(b.d_wrow, proj ? nullptr : bs->gain.p, A, (size_t)h->S * h->R, T, bs->pref.p);
     if (proj) BEAM_ANY(A, beamproj_weights_launch, nbeam, bs->par.p, bs->gain.p, bs->proj.p, bs->W.p, bs->st)
     HIPCHK(h, bs->launched(1));
-    if (beams || rows_used) BEAM_ANY(A, beam_launch, proj != nullptr, a, bs->st)
+    if (want_beams || want_used) BEAM_ANY(A, beam_launch, proj != nullptr, a, bs->st)
     HIPCHK(h, bs->launched(2));
-    HIPCHK(h, bs->beams.to_host(beams, nval, bs->st));
-    HIPCHK(h, bs->used.to_host(rows_used, nused, bs->st));
+    return PB_OK;
+}
+
+// Both calls, under the name w, on the call's own state bs: the first part above, then the copies to the host and the
+// wait for them.
+static int beam_call(pb_handle *h, const std::string &w, pb_beam_state *&bs, bool projecting, int stream, int nseg, int nbeam,
+                     const double *delay, const double *psi, const float *gain, const float *proj, const int32_t *shift,
+                     int tscr, int nout, float *beams, int32_t *rows_used)
+{
+    BeamCall c = {stream, nseg, nbeam, delay, psi, gain, proj, shift, tscr, nout, 0, 0, 0, 0};
+    if (int rc = beam_check(h, w, projecting, c)) return rc;
+    if (int rc = beam_queue(h, bs, c, beams != nullptr, rows_used != nullptr, nullptr)) return rc;
+    HIPCHK(h, bs->beams.to_host(beams, c.nval, bs->st));
+    HIPCHK(h, bs->used.to_host(rows_used, c.nused, bs->st));
     HIPCHK(h, bs->finish());
     return PB_OK;
 }

@@ -125,6 +125,7 @@ struct pb_handle {
     int coadd_slot = 0, coadd_last = 0;
     struct pb_corr_state *corr = nullptr;   // the correlator's job (pb_job.h; pb_correlate.hip), from its first call on
     struct pb_beam_state *beam = nullptr, *beamproj = nullptr;   // pb_beamform's and pb_beamform_proj's (pb_beamform.hip), likewise
+    struct pb_plane_state *plane = nullptr;                      // pb_beam_planes' own buffers (pb_beam_plane.hip), likewise
     FftTables ft = {};
     DagConsts dag = {}, dag_fb = {};   // D'Agostino constants for N = 500 (blocks) and N = 12500 (FFT rows, K4)
     int dag_bands = 0;               // 1: crossings located (flags decided without the cube root); -1: PB_DAG_BANDS=0; -2: search failed, fallback
@@ -163,6 +164,7 @@ PB_LOCAL int fail(pb_handle *h, int code, const std::string &msg);   // h = null
 PB_LOCAL hipError_t sync_all(pb_handle *h);
 PB_LOCAL void pb_correlate_free(pb_handle *h);                       // pb_correlate.hip: what pb_destroy releases
 PB_LOCAL void pb_beamform_free(pb_handle *h);                        // pb_beamform.hip: likewise, both calls' states
+PB_LOCAL void pb_beam_plane_free(pb_handle *h);                      // pb_beam_plane.hip: likewise
 
 template <class T>
 static hipError_t dmalloc(pb_handle *h, T **p, size_t n)

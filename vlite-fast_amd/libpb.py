@@ -64,7 +64,8 @@ EXPORTS = ["pb_config_default", "pb_create", "pb_destroy", "pb_last_error", "pb_
            "pb_search_subbands", "pb_search_subband_dm", "pb_search_subband_timers", "pb_search_set_rfi_chan",
            "pb_search_rfi_chan_info", "pb_correlate_info", "pb_correlate", "pb_correlate_gated", "pb_correlate_timers",
            "pb_imager_create", "pb_imager_destroy", "pb_imager_last_error", "pb_imager_set_vis", "pb_imager_run",
-           "pb_imager_timers", "pb_beamform", "pb_beamform_timers", "pb_beamform_proj", "pb_beamform_proj_timers"]
+           "pb_imager_timers", "pb_beamform", "pb_beamform_timers", "pb_beamform_proj", "pb_beamform_proj_timers",
+           "pb_beam_planes", "pb_beam_planes_timers"]
 CORR_RAW, CORR_KUR = 0, 1
 IMAGE_DELAY, IMAGE_PHASE = 0, 1
 IMAGE_PX = 8                 # pixels of the imaging kernel's tile (csrc/pb_image.hip: IMG_PX)
@@ -203,6 +204,8 @@ def load():
     L.pb_beamform_timers.argtypes = [vp, fp]
     L.pb_beamform_proj.argtypes = [vp, C.c_int, C.c_int, C.c_int, f64p, f64p, fp, fp, i32p, C.c_int, C.c_int, fp, i32p]
     L.pb_beamform_proj_timers.argtypes = [vp, fp]
+    L.pb_beam_planes.argtypes = [vp, C.c_int, C.c_int, C.c_int, f64p, f64p, fp, fp, i32p, C.c_int, C.c_int, fp, fp, fp, C.POINTER(vp)]
+    L.pb_beam_planes_timers.argtypes = [vp, fp]
     for n in EXPORTS:
         f = getattr(L, n)
         if f.restype is C.c_int or n in ("pb_create", "pb_query", "pb_sync"):
@@ -471,9 +474,9 @@ class PbHandle(object):
                                       _f32(beams), used.ctypes.data_as(i32p)))
         return beams, used
 
-    def _beam_arguments(self, nseg, delay, psi, gain, shift, tscr, nout):
-        """what beamform and beamform_proj share: the arguments as contiguous arrays of the library's types, nout (by
-        default as many output samples as fit) and the arrays the outputs arrive in"""
+    def _beam_arguments(self, nseg, delay, psi, gain, shift, tscr, nout, outputs=True):
+        """what the beam calls share: the arguments as contiguous arrays of the library's types, nout (by default as many
+        output samples as fit) and, unless outputs=False, the arrays that beamform's outputs arrive in"""
         delay = np.ascontiguousarray(np.atleast_2d(np.asarray(delay, np.float64)))
         if delay.ndim != 2 or delay.shape[1] != self.nant:
             raise ValueError("delay must be [nbeam][%d]" % self.nant)
@@ -494,6 +497,8 @@ class PbHandle(object):
             top = int(shift.max()) if shift is not None else 0
             nout = (nseg * self.rows - top) // tscr if tscr > 0 else 0
         nout = int(nout)
+        if not outputs:
+            return delay, psi, gain, shift, nout, None, None
         shape = (max(nbeam, 1), max(nout, 1))              # (a refused call still needs arrays to point at)
         beams = np.empty(shape + (4, NCHANOUT), np.float32)
         used = np.empty(shape + (NCHANOUT,), np.int32)
@@ -528,6 +533,43 @@ class PbHandle(object):
         ms = np.zeros(3, np.float32)
         self._chk(self._L.pb_beamform_proj_timers(self._h, _f32(ms)))
         return float(ms[0]), float(ms[1]), float(ms[2])
+
+    # ---- beam planes (include/pb_hip.h: pb_beam_planes; needs coherence=True)
+    def beam_planes(self, stream, nseg, delay, psi=None, gain=None, proj=None, shift=None, tscr=1, nout=None, level=None,
+                    to_host=True):
+        """The beams of beamform() (proj=None) or beamform_proj() as zero-mean, unit-variance fp32 planes that stay on the
+        device: AA + BB per (beam, output sample, channel), rescaled to a full window's rows, over a level per (beam,
+        channel), less 1, times sqrt(2 tscr).  level: float32 [nbeam][4096], the level to divide by, or None: the planes'
+        own mean.  -> (planes float32 [nbeam][nout][4096], or None with to_host=False; the device address of the same,
+        valid until the handle's next beam call; level_out float32 [nbeam][4096], the planes' own mean either way).  Beam
+        b's plane starts at address + b * nout * 4096 * 4: what Searcher.push_plane(device_ptr=...) takes."""
+        delay, psi, gain, shift, nout, _, _ = self._beam_arguments(nseg, delay, psi, gain, shift, tscr, nout, outputs=False)
+        nbeam = delay.shape[0]
+        if proj is not None:
+            proj = np.ascontiguousarray(proj, np.complex64)
+            if proj.shape != (2, NCHANOUT, self.nant, self.nant):
+                raise ValueError("proj must be [2][%d][%d][%d]" % (NCHANOUT, self.nant, self.nant))
+        if level is not None:
+            level = np.ascontiguousarray(level, np.float32)
+            if level.shape != (nbeam, NCHANOUT):
+                raise ValueError("level must be [%d][%d]" % (nbeam, NCHANOUT))
+        planes = np.empty((max(nbeam, 1), max(nout, 1), NCHANOUT), np.float32) if to_host else None
+        level_out = np.empty((max(nbeam, 1), NCHANOUT), np.float32)
+        ptr = C.c_void_p()
+        f64p, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        self._chk(self._L.pb_beam_planes(self._h, stream, nseg, nbeam, delay.ctypes.data_as(f64p),
+                                         psi.ctypes.data_as(f64p) if psi is not None else None, _f32(gain),
+                                         proj.ctypes.data_as(C.POINTER(C.c_float)) if proj is not None else None,
+                                         shift.ctypes.data_as(i32p) if shift is not None else None, tscr, nout,
+                                         _f32(level), _f32(level_out), _f32(planes), C.byref(ptr)))
+        return planes, int(ptr.value), level_out
+
+    def beam_planes_timers(self):
+        """device ms of the last beam_planes call: (uploads + weights + row counts, beam kernel, level and plane kernels,
+        copies to the host)"""
+        ms = np.zeros(4, np.float32)
+        self._chk(self._L.pb_beam_planes_timers(self._h, _f32(ms)))
+        return tuple(float(x) for x in ms)
 
     def profile(self, enable=True):
         self._chk(self._L.pb_profile(self._h, int(enable)))
