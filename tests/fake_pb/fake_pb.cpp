@@ -2,7 +2,7 @@
 // tests/test_native_host_cpu.py: exactly the entry points of include/pb_hip.h that the program calls, no HIP,
 // everything in host memory.  Linked in place of the library (make -C vlite-fast_amd/csrc host-standin), not injected.
 //
-// pb_submit_vdif_at deframes on the host by the placement rule of pb_api.hip / vdif.deframe_block.  The "filterbank
+// pb_submit_vdif_at deframes on the host by the placement rule of pb_stage.hip / vdif.deframe_block.  The "filterbank
 // bytes" of a segment are a FOLD of its samples, so that every sample of the second and its position reach the output
 // (a prefix of the samples would cover the first few frames only):
 //     out[seg][j] = sum over i in [0, seg_samples), i % trim == j, of (2 * (i / trim) + 1) * x[seg * seg_samples + i]

@@ -91,7 +91,12 @@ def test_shipped_library_reads_exactly_the_documented_switches():
         if fn.endswith((".hip", ".h")):
             seen |= set(re.findall(r'(?:getenv|env_int)\("([A-Z0-9_]+)"', open(os.path.join(csrc, fn)).read()))
     assert seen <= allowed, seen - allowed
-    txt = open(os.path.join(csrc, "pb_api.hip")).read()
+    # one source holds every read of the environment, so that the experiments library differs from this one in one object
+    for fn in os.listdir(csrc):
+        if fn.endswith((".hip", ".h", ".inc")) and fn != "pb_handle.hip":
+            src = open(os.path.join(csrc, fn)).read()
+            assert "getenv(" not in src and "env_int(" not in src, fn
+    txt = open(os.path.join(csrc, "pb_handle.hip")).read()
     i = txt.index('getenv("PB_SKIP")')
     assert "#if PB_EXPERIMENTS" in txt[max(0, i - 200):i]       # the one PB_SKIP read sits behind the build switch
     assert txt.count('getenv("PB_SKIP")') == 2                   # (both on that one line)
@@ -101,6 +106,46 @@ def test_shipped_library_reads_exactly_the_documented_switches():
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     for name in SHIPPED_SWITCHES:
         assert "| `%s` |" % name in doc, name
+
+
+def _function_body(txt, signature):
+    """the text between the braces of the function whose definition starts with `signature`"""
+    i = txt.index("{", txt.index(signature))
+    depth, j = 0, i
+    while True:
+        depth += {"{": 1, "}": -1}.get(txt[j], 0)
+        if depth == 0:
+            return txt[i + 1:j]
+        j += 1
+
+
+def test_the_handle_side_releases_nothing_by_hand():
+    """The channeliser handle and the jobs beside it (csrc/pb_*.hip and their headers) hold what they take from the HIP
+    runtime in members that own it (csrc/pb_own.h): a free or destroy call appears only in those owner types, in
+    job_free (pb_job.h: a job's stream and events) and in pb_host_free, which releases the CALLER'S memory.  pb_destroy
+    in particular keeps no list of members."""
+    import glob
+    import re
+    csrc = os.path.join(ROOT, "vlite-fast_amd", "csrc")
+    calls = re.compile(r"\b(hipFree|hipHostFree|hipEventDestroy|hipStreamDestroy)\(")
+    files = sorted(glob.glob(os.path.join(csrc, "pb_*.hip"))) + [os.path.join(csrc, f) for f in ("pb_internal.h", "pb_job.h", "pb_beam.h")]
+    assert len(files) >= 12
+    destroy = None
+    for path in files:
+        txt = open(path).read()
+        fn = os.path.basename(path)
+        if fn == "pb_job.h":
+            txt = txt.replace(_function_body(txt, "static void job_free("), "")
+        if 'extern "C" void pb_host_free(' in txt:
+            body = _function_body(txt, 'extern "C" void pb_host_free(')
+            assert calls.findall(body) == ["hipHostFree"]
+            txt = txt.replace(body, "")
+        if 'extern "C" void pb_destroy(' in txt:
+            destroy = _function_body(txt, 'extern "C" void pb_destroy(')
+        assert not calls.search(txt), "%s: %s" % (fn, sorted(set(calls.findall(txt))))
+    assert destroy is not None and "delete h" in destroy and not calls.search(destroy)
+    assert destroy.count(";") <= 12, "pb_destroy has grown a list again"
+    assert calls.search(open(os.path.join(csrc, "pb_own.h")).read())      # (the owners are where the calls are)
 
 
 def test_tree_order_of_the_library_equals_the_python_plan():

@@ -1,5 +1,5 @@
 """The taps = 4 chain (k_channelize_pfb, k_pfb_weights, k_pfb_history, the two history slots and their ordering in
-pb_api.hip) against tests/pfb_ref.py, an enumerated set of small cases, each chosen for one code path: every RFI mode,
+pb_process.hip) against tests/pfb_ref.py, an enumerated set of small cases, each chosen for one code path: every RFI mode,
 one and two output pols, 8 / 4 / 2 bits; row counts with their own detect chunking and XCD row map; two antennas in
 one handle; calls shorter than max_seg; reset_history / reset_bandpass of one antenna of two; a stream that starts
 with no data and dropped frames in the carried rows; the injected pulse.  Every comparison is exact: the code bytes of

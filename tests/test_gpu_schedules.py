@@ -1,4 +1,4 @@
-"""The stream graph of pb_process (csrc/pb_api.hip: five streams, eight events, branches by mode) under every
+"""The stream graph of pb_process (csrc/pb_process.hip: five streams, eight events, branches by mode) under every
 scheduling mode the library offers, at production size: batches of five full-size segments (R = 1024, half a second
 of one antenna each) through
     buffer sets 1 / 2 / 3  x  detect beside the next channeliser or behind its own (PB_OVERLAP_DETECT)

@@ -3,7 +3,7 @@
 # of the tree into build/variants/libpb_<name>.so (select with PB_LIBPATH).  usage:
 #   tools/build_variants.sh k_detect3.hip noB="-DD3_DBG=2" d8="-DD3_DEPTH=8" ...
 # Everything that makes results INVALID lives in such builds only (CH_ABL, FFT_ABL, D2_ABL, and PB_SKIP behind
-# -DPB_EXPERIMENTS=1: `tools/build_variants.sh pb_api.hip exp="-DPB_EXPERIMENTS=1"` or `make -C vlite-fast_amd/csrc exp`).
+# -DPB_EXPERIMENTS=1: `tools/build_variants.sh pb_handle.hip exp="-DPB_EXPERIMENTS=1"` or `make -C vlite-fast_amd/csrc exp`).
 set -e
 cd "$(dirname "$0")/../vlite-fast_amd/csrc"
 src=$1; shift

@@ -1,7 +1,8 @@
 # Occupancy emulation (results INVALID: LDS accesses beyond the allocation are dropped): the 128-register channeliser
 # (-DFFT_LEAN, two-kernel path) launched with less LDS than its exchange needs, so that the dispatcher packs it the
 # way a split-exchange kernel of that footprint would be packed -- what would 3 channeliser workgroups + 1 detect
-# workgroup per CU be worth to the pipelined step?   needs: tools/build_variants.sh k_channelize.hip lean="-DFFT_LEAN"
+# workgroup per CU be worth to the pipelined step?   needs: tools/build_variant_multi.sh lean "-DFFT_LEAN" k_channelize.hip pb_handle.hip
+# (pb_handle.hip holds every read of the environment, PB_LEAN_LDS among them, behind the same flag)
 # DEPENDS ON gfx950's LDS bounds behaviour (out-of-range LDS accesses of a wave are dropped / return 0, no fault) and must
 # run ONLY with the FFT_LEAN variant build (the one that reads PB_LEAN_LDS): never point it at another library.
 run() { python bench.py --full --steps 40 --warmup 5 --regions 3 --no-extras --no-cpu-baseline --no-power 2>/dev/null | python -c "

@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void k_coadd_local_codes(const uint8_t *__rest
 hipError_t launch_coadd_local_codes(pb_handle *h, int nseg, float *d_sum, int accumulate, hipStream_t st)
 {
     const int stream = h->cfg.rfi_mode == 0 ? 0 : 1;
-    const uint8_t *codes = h->set().d_codes + (size_t)stream * h->S * h->trim;
+    const uint8_t *codes = h->set().d_codes.p + (size_t)stream * h->S * h->trim;
     k_coadd_local_codes<<<1024, 256, 0, st>>>(codes, (size_t)2 * h->S * h->trim, h->A, d_sum, h->ave_per_seg, h->trim,
                                               nseg, h->cfg.npol, h->cfg.nbit, h->R / PB_NSCRUNCH, accumulate);
     return hipGetLastError();

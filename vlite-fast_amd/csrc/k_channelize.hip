@@ -362,20 +362,20 @@ hipError_t launch_channelize(pb_handle *h, int nseg, int inject_now)
     if (nseg <= 0) return hipSuccess;
     const pb_handle::BufSet &b = h->set();
     ChanArgs a;
-    a.in = b.d_in;
+    a.in = b.d_in.p;
     a.in_ant_stride = (size_t)h->S * 2 * h->seg_samples;
     a.seg_samples = h->seg_samples;
-    a.wrow = b.d_wrow;
+    a.wrow = b.d_wrow.p;
     a.rowmask = pb_rowmask(h);
     a.wrow_ant_stride = (size_t)h->S * h->R;
-    a.Praw = b.d_Praw;
-    a.Pkur = b.d_Pkur;
+    a.Praw = b.d_Praw.p;
+    a.Pkur = b.d_Pkur.p;
     a.p_ant_stride = (size_t)h->S * 2 * h->R * PB_NCHANOUT;
-    a.tw2 = h->ft.tw2;
-    a.tw3 = h->ft.tw3;
-    a.post = h->ft.post;
-    a.postc = h->ft.postc;
-    a.frb.delays = (inject_now > 0) ? h->d_frb_delays : nullptr;
+    a.tw2 = h->ft.tw2.p;
+    a.tw3 = h->ft.tw3.p;
+    a.post = h->ft.post.p;
+    a.postc = h->ft.postc.p;
+    a.frb.delays = (inject_now > 0) ? h->d_frb_delays.p : nullptr;
     a.frb.width = h->frb_width;
     a.frb.amp = h->frb_amp;
 #ifdef KUR_STAMP
@@ -387,11 +387,11 @@ hipError_t launch_channelize(pb_handle *h, int nseg, int inject_now)
     a.R = h->R;
     a.rfi_mode = h->cfg.rfi_mode;
     a.inject_now = inject_now;
-    a.flags = b.d_flags;
+    a.flags = b.d_flags.p;
     a.flags_ant_stride = (size_t)h->S * h->nblk_seg;
-    a.wrow_out = b.d_wrow;
+    a.wrow_out = b.d_wrow.p;
     a.rowmask_out = pb_rowmask(h);
-    a.dag = h->d_dag;
+    a.dag = h->d_dag.p;
     if (pb_fused_kurtosis(h)) {
         // one workgroup per row (both pols): it computes the row's flags itself
         dim3 gk((unsigned)h->R, (unsigned)nseg, (unsigned)h->A);
@@ -405,7 +405,7 @@ hipError_t launch_channelize(pb_handle *h, int nseg, int inject_now)
         return hipGetLastError();
     }
 #ifdef FFT_LEAN
-    static const int lean_lds = getenv("PB_LEAN_LDS") ? atoi(getenv("PB_LEAN_LDS")) : M_HALF * 8;
+    static const int lean_lds = pb_lean_lds(M_HALF * 8);
     k_channelize<<<grid, 256, lean_lds, h->stream>>>(a);
 #else
     k_channelize<<<grid, 256, 0, h->stream>>>(a);
@@ -455,6 +455,6 @@ hipError_t launch_channelize_f32(pb_handle *h, const float *d_x, int nrows, int 
 {
     hipError_t e = launch_channelize(h, 0, 0);  // validates the compile-time constants
     if (e != hipSuccess) return e;
-    k_channelize_f32<<<nrows, 256, 0, h->stream>>>(d_x, taps, h->ft.taps, d_out, h->ft.tw2, h->ft.tw3, h->ft.post);
+    k_channelize_f32<<<nrows, 256, 0, h->stream>>>(d_x, taps, h->ft.taps.p, d_out, h->ft.tw2.p, h->ft.tw3.p, h->ft.post.p);
     return hipGetLastError();
 }

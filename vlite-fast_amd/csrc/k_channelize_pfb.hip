@@ -35,7 +35,6 @@
 #ifndef PFB_ROW_LDS
 #define PFB_ROW_LDS 12528    // 12500 bytes + up to 12 of alignment slack, padded to 16
 #endif
-#define PFB_HIST_STRIDE 12512
 #ifndef PFB_STAGE_DMA
 #define PFB_STAGE_DMA 1      // rows go to LDS by global_load_lds_dwordx4 (0: through registers; timing experiments)
 #endif
@@ -367,8 +366,8 @@ hipError_t launch_pfb_weights(pb_handle *h, int nseg)
     const int nrows = nseg * h->R;
     dim3 g((nrows + 255) / 256, h->A);
     k_pfb_weights<<<g, 256, 0, h->stream>>>(pb_rowmask(h), (size_t)h->S * h->R,
-                                            h->d_hist_flags + (size_t)h->hist_rd * h->A * 3 * PB_BLK_PER_FFT, h->d_tapE,
-                                            h->set().d_wrow, nrows);
+                                            h->d_hist_flags.p + (size_t)h->hist_rd * h->A * 3 * PB_BLK_PER_FFT, h->d_tapE.p,
+                                            h->set().d_wrow.p, nrows);
     return hipGetLastError();
 }
 
@@ -376,25 +375,25 @@ hipError_t launch_channelize_pfb(pb_handle *h, int nseg, int inject_now)
 {
     const pb_handle::BufSet &b = h->set();
     PfbArgs a;
-    a.in = b.d_in;
+    a.in = b.d_in.p;
     a.in_ant_stride = (size_t)h->S * 2 * h->seg_samples;
     a.seg_samples = h->seg_samples;
-    a.hist = h->d_hist_in + (size_t)h->hist_rd * h->A * 2 * 3 * PFB_HIST_STRIDE;      // the slot this batch reads
-    a.flags = b.d_flags;
+    a.hist = h->d_hist_in.p + (size_t)h->hist_rd * h->A * 2 * 3 * PFB_HIST_STRIDE;      // the slot this batch reads
+    a.flags = b.d_flags.p;
     a.flags_ant_stride = (size_t)h->S * h->nblk_seg;
-    a.hflags = h->d_hist_flags + (size_t)h->hist_rd * h->A * 3 * PB_BLK_PER_FFT;
-    a.hvalid = h->d_hist_valid + (size_t)h->hist_rd * h->A * 3;
-    a.wrow = b.d_wrow;
+    a.hflags = h->d_hist_flags.p + (size_t)h->hist_rd * h->A * 3 * PB_BLK_PER_FFT;
+    a.hvalid = h->d_hist_valid.p + (size_t)h->hist_rd * h->A * 3;
+    a.wrow = b.d_wrow.p;
     a.rowmask = pb_rowmask(h);
     a.wrow_ant_stride = (size_t)h->S * h->R;
-    a.fir = h->ft.taps_n;
-    a.Praw = b.d_Praw;
-    a.Pkur = b.d_Pkur;
+    a.fir = h->ft.taps_n.p;
+    a.Praw = b.d_Praw.p;
+    a.Pkur = b.d_Pkur.p;
     a.p_ant_stride = (size_t)h->S * 2 * h->R * PB_NCHANOUT;
-    a.tw2 = h->ft.tw2;
-    a.tw3 = h->ft.tw3;
-    a.postc = h->ft.postc;
-    a.frb.delays = (inject_now > 0) ? h->d_frb_delays : nullptr;
+    a.tw2 = h->ft.tw2.p;
+    a.tw3 = h->ft.tw3.p;
+    a.postc = h->ft.postc.p;
+    a.frb.delays = (inject_now > 0) ? h->d_frb_delays.p : nullptr;
     a.frb.width = h->frb_width;
     a.frb.amp = h->frb_amp;
     a.frb.since = 0;
@@ -414,10 +413,10 @@ hipError_t launch_pfb_history(pb_handle *h, int nseg)
     const int wr = h->hist_rd ^ 1;       // the slot the NEXT batch will read
     const pb_handle::BufSet &b = h->set();
     dim3 gh(3, 2, h->A);
-    k_pfb_history<<<gh, 256, 0, h->stream>>>(b.d_in, (size_t)h->S * 2 * h->seg_samples, h->seg_samples, b.d_flags,
+    k_pfb_history<<<gh, 256, 0, h->stream>>>(b.d_in.p, (size_t)h->S * 2 * h->seg_samples, h->seg_samples, b.d_flags.p,
                                              (size_t)h->S * h->nblk_seg,
-                                             h->d_hist_in + (size_t)wr * h->A * 2 * 3 * PFB_HIST_STRIDE,
-                                             h->d_hist_flags + (size_t)wr * h->A * 3 * PB_BLK_PER_FFT,
-                                             h->d_hist_valid + (size_t)wr * h->A * 3, h->R, nrows);
+                                             h->d_hist_in.p + (size_t)wr * h->A * 2 * 3 * PFB_HIST_STRIDE,
+                                             h->d_hist_flags.p + (size_t)wr * h->A * 3 * PB_BLK_PER_FFT,
+                                             h->d_hist_valid.p + (size_t)wr * h->A * 3, h->R, nrows);
     return hipGetLastError();
 }

@@ -64,7 +64,7 @@ __global__ void k_inject_c64(float2 *__restrict__ X, size_t ant_stride, size_t s
 
 hipError_t launch_inject_c64(pb_handle *h, int nseg, int inject_now)
 {
-    if (inject_now <= 0 || !h->d_frb_delays) return hipSuccess;
+    if (inject_now <= 0 || !h->d_frb_delays.p) return hipSuccess;
     const size_t pol_stride = (size_t)h->R * PB_NCHAN;
     const size_t seg_stride = 2 * pol_stride;
     const size_t ant_stride = (size_t)h->S * seg_stride;
@@ -72,11 +72,11 @@ hipError_t launch_inject_c64(pb_handle *h, int nseg, int inject_now)
     const pb_handle::BufSet &b = h->set();
     dim3 grid((PB_NCHANOUT + 255) / 256, nseg, h->A);
     if (h->cfg.rfi_mode != 1)
-        k_inject_c64<<<grid, 256, 0, h->stream>>>(b.d_Xraw, ant_stride, seg_stride, pol_stride,
-                                                  h->d_frb_delays, inject_now, width, h->frb_amp, h->R);
+        k_inject_c64<<<grid, 256, 0, h->stream>>>(b.d_Xraw.p, ant_stride, seg_stride, pol_stride,
+                                                  h->d_frb_delays.p, inject_now, width, h->frb_amp, h->R);
     if (h->cfg.rfi_mode != 0)
-        k_inject_c64<<<grid, 256, 0, h->stream>>>(b.d_Xkur, ant_stride, seg_stride, pol_stride,
-                                                  h->d_frb_delays, inject_now, width, h->frb_amp, h->R);
+        k_inject_c64<<<grid, 256, 0, h->stream>>>(b.d_Xkur.p, ant_stride, seg_stride, pol_stride,
+                                                  h->d_frb_delays.p, inject_now, width, h->frb_amp, h->R);
     return hipGetLastError();
 }
 
@@ -114,13 +114,13 @@ hipError_t launch_detect(pb_handle *h, int nseg, int)
         const size_t per_ant = (size_t)nseg * 2 * h->R;
         for (int st = 0; st < 2; ++st) {
             if (st == 0 ? h->cfg.rfi_mode == 1 : h->cfg.rfi_mode == 0) continue;
-            const float2 *X = st ? b.d_Xkur : b.d_Xraw;
-            float *P = st ? b.d_Pkur : b.d_Praw;
+            const float2 *X = st ? b.d_Xkur.p : b.d_Xraw.p;
+            float *P = st ? b.d_Pkur.p : b.d_Praw.p;
             for (int ant = 0; ant < h->A; ++ant) {
                 const size_t rp0 = (size_t)ant * h->S * 2 * h->R;
                 const size_t nthreads = per_ant * (PB_NCHANOUT / 4);
                 k_power_c64<<<(unsigned)((nthreads + 255) / 256), 256, 0, h->stream>>>(
-                    X + rp0 * PB_NCHAN, P + rp0 * PB_NCHANOUT, b.d_wrow + (size_t)ant * h->S * h->R, per_ant, h->R, st);
+                    X + rp0 * PB_NCHAN, P + rp0 * PB_NCHANOUT, b.d_wrow.p + (size_t)ant * h->S * h->R, per_ant, h->R, st);
             }
         }
         hipError_t e = hipGetLastError();
@@ -146,7 +146,7 @@ hipError_t launch_coadd_local(pb_handle *h, int nseg, float *d_sum, int accumula
 {
     const int stream = h->cfg.rfi_mode == 0 ? 0 : 1;
     const size_t n = (size_t)nseg * h->ave_per_seg;
-    const float *ave = h->set().d_ave + (size_t)stream * h->S * h->ave_per_seg;
+    const float *ave = h->set().d_ave.p + (size_t)stream * h->S * h->ave_per_seg;
     k_coadd_local<<<1024, 256, 0, st>>>(ave, (size_t)2 * h->S * h->ave_per_seg, h->A, d_sum, n,
                                                accumulate);
     return hipGetLastError();

@@ -601,12 +601,12 @@ hipError_t launch_detect_pow(pb_handle *h, int nseg)
 {
     const pb_handle::BufSet &b = h->set();
     Detect2Args a;
-    a.P[0] = b.d_Praw;
-    a.P[1] = b.d_Pkur;
-    a.wrow = b.d_wrow;
-    a.bp = h->d_bp;
-    a.codes = b.d_codes;
-    a.ave = h->cfg.keep_ave ? b.d_ave : nullptr;
+    a.P[0] = b.d_Praw.p;
+    a.P[1] = b.d_Pkur.p;
+    a.wrow = b.d_wrow.p;
+    a.bp = h->d_bp.p;
+    a.codes = b.d_codes.p;
+    a.ave = h->cfg.keep_ave ? b.d_ave.p : nullptr;
     a.ave_target = h->cfg.keep_ave ? b.d_coadd_target : nullptr;
     a.target_stream = h->cfg.rfi_mode == 0 ? 0 : 1;
     a.trim = h->trim;

@@ -312,12 +312,12 @@ hipError_t launch_detect_coh(pb_handle *h, int nseg)
 {
     const pb_handle::BufSet &b = h->set();
     DetectCohArgs a;
-    a.X[0] = (const float2 *)b.d_Praw;
-    a.X[1] = (const float2 *)b.d_Pkur;
-    a.wrow = b.d_wrow;
-    a.bp = h->d_bp;
-    a.codes = b.d_codes;
-    a.ave = h->cfg.keep_ave ? b.d_ave : nullptr;
+    a.X[0] = (const float2 *)b.d_Praw.p;
+    a.X[1] = (const float2 *)b.d_Pkur.p;
+    a.wrow = b.d_wrow.p;
+    a.bp = h->d_bp.p;
+    a.codes = b.d_codes.p;
+    a.ave = h->cfg.keep_ave ? b.d_ave.p : nullptr;
     a.trim = h->trim;
     a.ave_per_seg = h->ave_per_seg;
     a.S = h->S;

@@ -245,8 +245,8 @@ hipError_t launch_kurtosis_flag(pb_handle *h, int nseg, bool write_f32)
         if (!write_f32) return hipSuccess;
         for (int a = 0; a < h->A; ++a) {
             const size_t n4 = (size_t)nseg * 2 * h->seg_samples / 4;
-            k_unpack<<<2048, 256, 0, h->stream>>>(b.d_in + a * in_ant_stride,
-                                                  b.d_fraw + a * in_ant_stride, n4);
+            k_unpack<<<2048, 256, 0, h->stream>>>(b.d_in.p + a * in_ant_stride,
+                                                  b.d_fraw.p + a * in_ant_stride, n4);
         }
         return hipGetLastError();
     }
@@ -254,11 +254,11 @@ hipError_t launch_kurtosis_flag(pb_handle *h, int nseg, bool write_f32)
     const size_t wrow_ant = (size_t)h->S * h->R;
     // row statistics (K4) live behind the six per-block planes of every antenna
     const size_t nrow_cap = (size_t)h->S * h->R;
-    float *stats_fb = b.d_stats ? b.d_stats + (size_t)h->A * 6 * nblk_cap : nullptr;
+    float *stats_fb = b.d_stats.p ? b.d_stats.p + (size_t)h->A * 6 * nblk_cap : nullptr;
 #define PB_KURT_LAUNCH(F32, FB)                                                                                   \
     k_kurtosis_row<F32, FB><<<grid, 256, 0, h->stream>>>(                                                          \
-        b.d_in, in_ant_stride, h->seg_samples, h->R, b.d_flags, nblk_cap, b.d_wrow, pb_rowmask(h), wrow_ant,    \
-        b.d_stats, nblk_cap, F32 ? b.d_fraw : nullptr, F32 ? b.d_fkur : nullptr,                                \
+        b.d_in.p, in_ant_stride, h->seg_samples, h->R, b.d_flags.p, nblk_cap, b.d_wrow.p, pb_rowmask(h), wrow_ant,    \
+        b.d_stats.p, nblk_cap, F32 ? b.d_fraw.p : nullptr, F32 ? b.d_fkur.p : nullptr,                                \
         F32 && h->cfg.rfi_mode == 2 ? 1 : 0, h->dag, h->dag_fb, stats_fb, nrow_cap)
     if (write_f32) {
         if (stats_fb) PB_KURT_LAUNCH(true, true); else PB_KURT_LAUNCH(true, false);
@@ -294,8 +294,8 @@ __global__ __launch_bounds__(256) void k_deframe(const uint8_t *__restrict__ blo
 hipError_t launch_deframe(pb_handle *h, int ant, int seg0, size_t nframes_per_thread)
 {
     dim3 grid((unsigned)nframes_per_thread, 2);
-    uint8_t *dst = h->set().d_in + (size_t)ant * h->S * 2 * h->seg_samples;
-    k_deframe<<<grid, 256, 0, h->stream>>>(h->d_vdif, h->d_frame_idx, dst, nframes_per_thread,
+    uint8_t *dst = h->set().d_in.p + (size_t)ant * h->S * 2 * h->seg_samples;
+    k_deframe<<<grid, 256, 0, h->stream>>>(h->d_vdif.p, h->d_frame_idx.p, dst, nframes_per_thread,
                                            h->seg_samples, seg0);
     return hipGetLastError();
 }

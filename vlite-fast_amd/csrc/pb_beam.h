@@ -17,26 +17,6 @@ struct BeamArgs {
     int S, R, T, nbeam, tscr, nout, spc;   // spc: output samples per workgroup
 };
 
-// pinned host memory that is freed with the struct it is a member of: the matrices go to the device from here, so that
-// their upload is a DMA transfer that does not wait for the host
-struct PB_LOCAL PinnedProj {
-    float2 *p = nullptr;
-    size_t cap = 0;      // elements
-    PinnedProj() = default;
-    PinnedProj(PinnedProj &&) = delete;
-    ~PinnedProj() { if (p) (void)hipHostFree(p); }
-    hipError_t grow(size_t n)
-    {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipHostMalloc((void **)&p, n * sizeof(float2), hipHostMallocDefault);
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-};
-
 struct PB_LOCAL pb_beam_state : PbJob<3> {      // stages: uploads + weights + row counts, beam kernel, copy to the host
     DevBuf<double> par;                  // [2][BEAM_MAX_BEAMS * PB_SPECTRA_MAX_ANT]: delay / 12500, psi
     DevBuf<float> gain;                  // [BEAM_MAX_BEAMS * PB_SPECTRA_MAX_ANT]
@@ -48,7 +28,8 @@ struct PB_LOCAL pb_beam_state : PbJob<3> {      // stages: uploads + weights + r
     std::vector<double> h_par;
     std::vector<float> h_gain;
     std::vector<int32_t> h_shift;
-    PinnedProj h_proj;                   // [2][A][A][4096], the device's layout
+    PinBuf<float2> h_proj;               // [2][A][A][4096], the device's layout; pinned, so that the matrices' upload
+                                         // is a DMA transfer that does not wait for the host
 };
 
 // a call's arguments, and what beam_check works out from them

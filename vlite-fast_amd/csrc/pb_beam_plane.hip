@@ -111,9 +111,8 @@ struct PB_LOCAL pb_plane_state {
     DevBuf<float> level_in;      // [nbeam][4096] the caller's
     DevBuf<double> psum;         // [nbeam][nchunk][4096]
     DevBuf<int32_t> pcnt;
-    hipEvent_t ev = nullptr;     // the level and plane kernels end here
+    Event ev;                    // the level and plane kernels end here
     float ms[4] = {};
-    ~pb_plane_state() { if (ev) (void)hipEventDestroy(ev); }
 };
 
 void pb_beam_plane_free(pb_handle *h)
@@ -138,7 +137,7 @@ extern "C" int pb_beam_planes(pb_handle *h, int stream, int nseg, int nbeam, con
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (!h->plane) h->plane = new pb_plane_state;
     pb_plane_state *ps = h->plane;
-    if (!ps->ev) HIPCHK(h, hipEventCreate(&ps->ev));
+    HIPCHK(h, ps->ev.create(hipEventDefault));      // (timed)
     const int nchunk = (nout + PLANE_CHUNK - 1) / PLANE_CHUNK;
     HIPCHK(h, ps->planes.grow(h, c.nused));
     HIPCHK(h, ps->level.grow(h, nlev));
@@ -169,14 +168,14 @@ extern "C" int pb_beam_planes(pb_handle *h, int stream, int nseg, int nbeam, con
     k_beam_level<<<dim3(PB_NCHANOUT / PLANE_LANES, nbeam), PLANE_LANES, 0, bs->st>>>(ps->psum.p, ps->pcnt.p, nchunk, ps->level.p);
     if (!level_in) k_beam_plane<false, true><<<grid, PLANE_LANES, 0, bs->st>>>(a);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(ps->ev, bs->st));
+    HIPCHK(h, hipEventRecord(ps->ev.e, bs->st));
     HIPCHK(h, ps->level.to_host(level_out, nlev, bs->st));
     HIPCHK(h, ps->planes.to_host(planes, c.nused, bs->st));
     HIPCHK(h, bs->finish());
     ps->ms[0] = bs->ms[0];
     ps->ms[1] = bs->ms[1];
-    HIPCHK(h, hipEventElapsedTime(&ps->ms[2], bs->ev[2], ps->ev));
-    HIPCHK(h, hipEventElapsedTime(&ps->ms[3], ps->ev, bs->ev[3]));
+    HIPCHK(h, hipEventElapsedTime(&ps->ms[2], bs->ev[2], ps->ev.e));
+    HIPCHK(h, hipEventElapsedTime(&ps->ms[3], ps->ev.e, bs->ev[3]));
     for (int k = 0; k < 3; ++k) bs->ms[k] = kept[k];
     if (d_planes) *d_planes = ps->planes.p;
     return PB_OK;

@@ -389,7 +389,7 @@ int beam_queue(pb_handle *h, pb_beam_state *&bs, const BeamCall &c, bool want_be
     const pb_handle::BufSet &b = h->set();
     // behind the set's channeliser and detect (ev_chan): whatever refills the set is queued by a later call, and this
     // one returns only when its own stream has drained
-    HIPCHK(h, hipStreamWaitEvent(bs->st, b.ev_chan, 0));
+    HIPCHK(h, hipStreamWaitEvent(bs->st, b.ev_chan.e, 0));
     HIPCHK(h, bs->mark(0));
     HIPCHK(h, bs->par.from_host(bs->h_par.data(), 2 * (size_t)n, bs->st));
     HIPCHK(h, bs->gain.from_host(bs->h_gain.data(), (size_t)n, bs->st));
@@ -397,7 +397,7 @@ int beam_queue(pb_handle *h, pb_beam_state *&bs, const BeamCall &c, bool want_be
     if (proj) HIPCHK(h, bs->proj.from_host(bs->h_proj.p, nproj, bs->st));
     if (more) HIPCHK(h, hipMemcpyAsync(more->dst, more->src, more->n * sizeof(float), hipMemcpyHostToDevice, bs->st));
     BeamArgs a;
-    a.X = (const float2 *)(c.stream == PB_CORR_KUR ? b.d_Pkur : b.d_Praw);
+    a.X = (const float2 *)(c.stream == PB_CORR_KUR ? b.d_Pkur.p : b.d_Praw.p);
     a.W = bs->W.p;
     a.shift = bs->shift.p;
     a.pref = count ? bs->pref.p : nullptr;
@@ -413,7 +413,7 @@ int beam_queue(pb_handle *h, pb_beam_state *&bs, const BeamCall &c, bool want_be
     // the plain call's weights go before its row counts, the projecting call's after them
     if (!proj) k_beam_weights<<<dim3(PB_NCHANOUT / 64, n), 64, 0, bs->st>>>(bs->par.p, bs->par.p + n, bs->gain.p, bs->W.p);
     if (count)
-        k_beam_prefix<<<proj ? 1 : nbeam, 64, 0, bs->st>>>(b.d_wrow, proj ? nullptr : bs->gain.p, A, (size_t)h->S * h->R, T, bs->pref.p);
+        k_beam_prefix<<<proj ? 1 : nbeam, 64, 0, bs->st>>>(b.d_wrow.p, proj ? nullptr : bs->gain.p, A, (size_t)h->S * h->R, T, bs->pref.p);
     if (proj) BEAM_ANY(A, beamproj_weights_launch, nbeam, bs->par.p, bs->gain.p, bs->proj.p, bs->W.p, bs->st)
     HIPCHK(h, bs->launched(1));
     if (want_beams || want_used) BEAM_ANY(A, beam_launch, proj != nullptr, a, bs->st)

@@ -30,8 +30,8 @@ static int no_coherence(pb_handle *h, const char *what)
 static hipError_t coadd_stream_after_detect(pb_handle *h, hipStream_t *cs)
 {
     *cs = h->s_coadd ? h->s_coadd : h->stream;
-    if (hipEventQuery(h->set().ev_chan) == hipSuccess) return hipSuccess;
-    return hipStreamWaitEvent(*cs, h->set().ev_chan, 0);
+    if (hipEventQuery(h->set().ev_chan.e) == hipSuccess) return hipSuccess;
+    return hipStreamWaitEvent(*cs, h->set().ev_chan.e, 0);
 }
 
 extern "C" int pb_coadd_local(pb_handle *h, int nseg, float *d_sum, int accumulate)
@@ -56,7 +56,7 @@ extern "C" int pb_coadd_local(pb_handle *h, int nseg, float *d_sum, int accumula
         StageTimer t(h, PB_ST_COADD);
         e = launch_coadd_local(h, nseg, d_sum, accumulate, cs);
         t.stop();
-        if (e == hipSuccess) e = hipEventRecord(b.ev_cl, cs);
+        if (e == hipSuccess) e = hipEventRecord(b.ev_cl.e, cs);
     }
     HIPCHK(h, e);
     return PB_OK;
@@ -77,7 +77,7 @@ extern "C" int pb_coadd_local_codes(pb_handle *h, int nseg, float *d_sum, int ac
     hipStream_t cs;
     HIPCHK(h, coadd_stream_after_detect(h, &cs));
     hipError_t e = launch_coadd_local_codes(h, nseg, d_sum, accumulate, cs);
-    if (e == hipSuccess) e = hipEventRecord(b.ev_cl, cs);      // (the set's next detect writes codes and planes alike)
+    if (e == hipSuccess) e = hipEventRecord(b.ev_cl.e, cs);      // (the set's next detect writes codes and planes alike)
     HIPCHK(h, e);
     return PB_OK;
 }
@@ -124,7 +124,7 @@ extern "C" int pb_coadd_local_tree(pb_handle *h, int nseg, const int32_t *ant_or
         const int a = ant_order[i];
         if (a < 0 || a >= h->A) return fail(h, PB_EINVAL, "pb_coadd_local_tree: antenna index out of range");
         leaves[i] = (b.d_coadd_target && a == 0) ? b.d_coadd_target
-                                                  : b.d_ave + ((size_t)a * 2 + stream) * h->S * h->ave_per_seg;
+                                                  : b.d_ave.p + ((size_t)a * 2 + stream) * h->S * h->ave_per_seg;
         if (leaves[i] == d_dst && n > 1) return fail(h, PB_EINVAL, "pb_coadd_local_tree: d_dst is one of the leaves");
     }
     hipStream_t cs;
@@ -137,7 +137,7 @@ extern "C" int pb_coadd_local_tree(pb_handle *h, int nseg, const int32_t *ant_or
         StageTimer t(h, PB_ST_COADD);
         e = launch_coadd_tree(leaves, n, d_dst, (size_t)nseg * h->ave_per_seg, cs);
         t.stop();
-        if (e == hipSuccess) e = hipEventRecord(b.ev_cl, cs);
+        if (e == hipSuccess) e = hipEventRecord(b.ev_cl.e, cs);
     }
     HIPCHK(h, e);
     return PB_OK;
@@ -186,7 +186,7 @@ extern "C" int pb_coadd_release(pb_handle *h)
     if (!h) return PB_EINVAL;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t cs = h->s_coadd ? h->s_coadd : h->stream;
-    HIPCHK(h, hipEventRecord(h->set().ev_cl, cs));      // what the set's next detect waits for before it writes the planes
+    HIPCHK(h, hipEventRecord(h->set().ev_cl.e, cs));      // what the set's next detect waits for before it writes the planes
     return PB_OK;
 }
 
@@ -194,10 +194,10 @@ extern "C" int pb_coadd_release(pb_handle *h)
 static int coadd_slots(pb_handle *h)
 {
     const size_t nb = (size_t)h->S * h->trim;
-    if (!h->d_coadd_codes) {
-        HIPCHK(h, dmalloc(h, &h->d_coadd_codes, 2 * nb));
-        HIPCHK(h, hipHostMalloc((void **)&h->h_coadd_codes, 2 * nb, hipHostMallocDefault));
-        for (int i = 0; i < 2; ++i) HIPCHK(h, hipEventCreateWithFlags(&h->ev_coadd[i], hipEventDisableTiming));
+    if (!h->d_coadd_codes.p) {
+        HIPCHK(h, h->d_coadd_codes.grow(h, 2 * nb));
+        HIPCHK(h, h->h_coadd_codes.grow(2 * nb));
+        for (Event &ev : h->ev_coadd) HIPCHK(h, ev.create());
         h->coadd_slot = 0;
     }
     return PB_OK;
@@ -222,12 +222,12 @@ extern "C" int pb_coadd_finish(pb_handle *h, int nseg, const float *d_sum, int n
     // requantise and copy out on the coadd stream, in order (the slot's previous copy-out, two calls
     // ago, went through the same stream)
     hipStream_t cs = h->s_coadd ? h->s_coadd : h->stream;
-    HIPCHK(h, launch_coadd_digitise(h, nseg, d_sum, scale, h->d_coadd_codes + slot * nb, cs));
-    HIPCHK(h, launch_copy_out(h->sched, h->h_coadd_codes + slot * nb, h->d_coadd_codes + slot * nb, (size_t)nseg * h->trim, cs));
-    HIPCHK(h, hipEventRecord(h->ev_coadd[slot], cs));
+    HIPCHK(h, launch_coadd_digitise(h, nseg, d_sum, scale, h->d_coadd_codes.p + slot * nb, cs));
+    HIPCHK(h, launch_copy_out(h->sched, h->h_coadd_codes.p + slot * nb, h->d_coadd_codes.p + slot * nb, (size_t)nseg * h->trim, cs));
+    HIPCHK(h, hipEventRecord(h->ev_coadd[slot].e, cs));
     if (codes_host) {
-        HIPCHK(h, hipEventSynchronize(h->ev_coadd[slot]));
-        memcpy(codes_host, h->h_coadd_codes + slot * nb, (size_t)nseg * h->trim);
+        HIPCHK(h, hipEventSynchronize(h->ev_coadd[slot].e));
+        memcpy(codes_host, h->h_coadd_codes.p + slot * nb, (size_t)nseg * h->trim);
     }
     return PB_OK;
 }
@@ -260,19 +260,19 @@ extern "C" int pb_coadd_publish(pb_handle *h, const uint8_t *d_codes, size_t nby
     h->coadd_slot ^= 1;
     h->coadd_last = slot;
     hipStream_t cs = h->s_coadd ? h->s_coadd : h->stream;
-    HIPCHK(h, launch_copy_out(h->sched, h->h_coadd_codes + slot * nb, d_codes, nbytes, cs));
-    HIPCHK(h, hipEventRecord(h->ev_coadd[slot], cs));
+    HIPCHK(h, launch_copy_out(h->sched, h->h_coadd_codes.p + slot * nb, d_codes, nbytes, cs));
+    HIPCHK(h, hipEventRecord(h->ev_coadd[slot].e, cs));
     return PB_OK;
 }
 
 extern "C" int pb_coadd_fetch_ptr(pb_handle *h, int age, const uint8_t **codes)
 {
     if (!h || !codes) return PB_EINVAL;
-    if (!h->d_coadd_codes) return fail(h, PB_ESTATE, "pb_coadd_fetch_ptr: no pb_coadd_finish yet");
+    if (!h->d_coadd_codes.p) return fail(h, PB_ESTATE, "pb_coadd_fetch_ptr: no pb_coadd_finish yet");
     if (age < 0 || age > 1) return fail(h, PB_EINVAL, "pb_coadd_fetch_ptr: age must be 0 (latest) or 1 (previous)");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int slot = age == 0 ? h->coadd_last : (h->coadd_last ^ 1);
-    HIPCHK(h, hipEventSynchronize(h->ev_coadd[slot]));
-    *codes = h->h_coadd_codes + (size_t)slot * h->S * h->trim;
+    HIPCHK(h, hipEventSynchronize(h->ev_coadd[slot].e));
+    *codes = h->h_coadd_codes.p + (size_t)slot * h->S * h->trim;
     return PB_OK;
 }

@@ -216,11 +216,11 @@ static int corr_run(pb_handle *h, int stream, int nseg, int ngate, int nrows, fl
     const pb_handle::BufSet &b = h->set();
     // behind the set's channeliser and detect (ev_chan); whatever refills the set is queued by a later call, and this
     // one returns only when its own stream has drained
-    HIPCHK(h, hipStreamWaitEvent(cs->st, b.ev_chan, 0));
+    HIPCHK(h, hipStreamWaitEvent(cs->st, b.ev_chan.e, 0));
     HIPCHK(h, cs->row0.from_host(cs->h_row0.data(), nrow0, cs->st));
     HIPCHK(h, cs->mark(0));
     CorrArgs a;
-    a.X = (const float2 *)(kur ? b.d_Pkur : b.d_Praw);
+    a.X = (const float2 *)(kur ? b.d_Pkur.p : b.d_Praw.p);
     a.row0 = cs->row0.p;
     a.pref = nullptr;
     a.vis = vis ? (float2 *)cs->vis.p : nullptr;
@@ -232,7 +232,7 @@ static int corr_run(pb_handle *h, int stream, int nseg, int ngate, int nrows, fl
     a.nrows = nrows;
     a.i0 = a.j0 = 0;
     if (kur && rows_used) {
-        k_corr_prefix<<<dim3(h->A, h->A), 64, 0, cs->st>>>(b.d_wrow, h->A, (size_t)h->S * h->R, T, cs->pref.p);
+        k_corr_prefix<<<dim3(h->A, h->A), 64, 0, cs->st>>>(b.d_wrow.p, h->A, (size_t)h->S * h->R, T, cs->pref.p);
         a.pref = cs->pref.p;
     }
     corr_launch_all(a, ngate, cs->st);

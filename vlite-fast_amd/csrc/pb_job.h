@@ -1,25 +1,10 @@
 // The host side of a call that runs beside the pipeline: on a stream of its own, in timed stages, on device buffers it
 // owns, back when its outputs have reached the host.  The correlator, the beamformer and the imager are such jobs: their
-// state derives from PbJob<stages>, holds its buffers as DevBuf members and is freed by job_free.
+// state derives from PbJob<stages>, holds its buffers as DevBuf members (pb_own.h) and is freed by job_free.
 #pragma once
 #include "pb_internal.h"
 
 #include <cmath>
-
-// a device buffer that is freed with the struct it is a member of: none can be forgotten at teardown
-template <class T>
-struct PB_LOCAL DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;      // elements
-    DevBuf() = default;
-    DevBuf(DevBuf &&) = delete;      // (nor copied)
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t grow(pb_handle *h, size_t n) { return dgrow(h, &p, &cap, n); }     // on demand; h->device_bytes follows
-    hipError_t alloc(size_t n) { cap = n; return hipMalloc((void **)&p, n * sizeof(T)); }     // once, without a handle
-    hipError_t from_host(const T *src, size_t n, hipStream_t st) { return hipMemcpyAsync(p, src, n * sizeof(T), hipMemcpyHostToDevice, st); }
-    // (dst = nullptr: an output the caller left out)
-    hipError_t to_host(void *dst, size_t n, hipStream_t st) const { return dst ? hipMemcpyAsync(dst, p, n * sizeof(T), hipMemcpyDeviceToHost, st) : hipSuccess; }
-};
 
 // a non-blocking stream, N stages between N + 1 events, and the stages' device times of the last call
 template <int N>
