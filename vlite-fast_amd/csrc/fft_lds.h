@@ -359,22 +359,30 @@ __device__ __forceinline__ void read_z_pairs(const f2 *buf, int k0, f2 (&za)[4],
 #ifndef PB_NT_STORES      // 0 ordinary, 1 non-temporal
 #define PB_NT_STORES 1
 #endif
-// four consecutive channels c4 .. c4 + 3 of the row whose plane starts at `row` (wave-uniform)
-__device__ __forceinline__ void store_plane4(float *row, int c4, float a, float b, float c, float d)
+// four consecutive channels at p, a pointer declared as global memory: an address that has been held in a register
+// across an empty asm statement is no longer known to be one, and its stores would become flat ones
+typedef __attribute__((address_space(1))) float pb_gfloat;
+__device__ __forceinline__ void store_plane4(pb_gfloat *p, float a, float b, float c, float d)
 {
     typedef float f4s __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(1))) f4s gf4s;
     const f4s v = {a, b, c, d};
 #ifdef CH_ABL
 #if CH_ABL & 2
-    if (a == 123.456f) *(f4s *)(row + c4) = v;      // (experiments: the stores are compiled but never executed)
+    if (a == 123.456f) *(gf4s *)p = v;      // (experiments: the stores are compiled but never executed)
     return;
 #endif
 #endif
 #if PB_NT_STORES
-    __builtin_nontemporal_store(v, (f4s *)(row + c4));
+    __builtin_nontemporal_store(v, (gf4s *)p);
 #else
-    *(f4s *)(row + c4) = v;
+    *(gf4s *)p = v;
 #endif
+}
+// four consecutive channels c4 .. c4 + 3 of the row whose plane starts at `row` (wave-uniform)
+__device__ __forceinline__ void store_plane4(float *row, int c4, float a, float b, float c, float d)
+{
+    store_plane4((pb_gfloat *)(row + c4), a, b, c, d);
 }
 
 __device__ __forceinline__ float cvt_sample_c(unsigned u) { return u == 0 ? 0.0f : (float)u / 128 - 1; }

@@ -18,6 +18,10 @@
 // divided by the row weight).  Only when some block is flagged does it run a second pass on the
 // zeroed data (or write +inf, "no data", if every block is flagged).
 //
+// FRB injection (inject_frb): k_channelize and k_channelize_kur hold no injection code; launch_channelize picks their
+// twins k_inject_chan and k_inject_chan_kur, the same text with the per-channel window test compiled in, for the calls
+// that have a pulse to inject.
+//
 // Coherence output (pb_config.coherence): the same kernels, instantiated with COH = true (k_coh_chan,
 // k_coh_chan_kur), store the complex in-band spectrum X (4096 x float2 per row and pol, after injection) in
 // place of |X|^2, undivided by the row weight; a row of weight 0 gets zeros in the excised plane.
@@ -104,15 +108,15 @@ __device__ __forceinline__ void stage_request(const ChanArgs &a, int tid, int se
 // is the first or the second float below x -- the second when x's mantissa field m is 0 or >= 0x400002
 // (m 2^-23 >= 1.5 + ...: the exact quotient m (1 - 2^-23 + 2^-46 - ...) lies below the midpoint) -- checked
 // against the IEEE division for every positive normal binary32 from 0x00800002 up (tools/check_div_full_weight.c);
-// smaller values, zeros and non-finite ones take the division.  4 instructions instead of 11.
-__device__ __forceinline__ float div_full_weight(float x)
-{
-    const unsigned b = __builtin_bit_cast(unsigned, x);
-    const unsigned m1 = (b & 0x7fffffu) - 1u;
-    const float fast = __builtin_bit_cast(float, b - (m1 >= 0x400001u ? 2u : 1u));
-    if (__builtin_expect(b - 0x00800002u >= 0x7f800000u - 0x00800002u, 0)) return x / 1.00000011920928955078125f;
-    return fast;
-}
+// smaller values, zeros and non-finite ones take the division.  For one value, with b the bits of x:
+//     m1 = (b & 0x7fffffu) - 1u;   quotient bits = b - (m1 >= 0x400001u ? 2u : 1u)
+//     unless b - 0x00800002u >= 0x7f800000u - 0x00800002u, which divides.
+// The kernels apply it to a thread's four powers at a time (div_row_weight4, spectrum_div4.h): five vector
+// instructions per value, then ONE range test for the four (the unsigned maximum of b - 0x00800002u) and a branch on a
+// vote of the wave, i.e. a scalar branch that ordinary data never takes -- about 7 issue slots per value.  With the
+// range test as an early return per value the compiler built an exec-mask diamond around every one of a thread's
+// sixteen values: 13 slots per value, 11 of the true division's instructions not executed but 8 of masking added.
+#include "spectrum_div4.h"
 
 // One transform of one (row, pol): ROLE 0 = raw spectrum (also fills the excised plane when the row
 // has no flagged block), ROLE 1 = excised spectrum (flagged blocks zeroed).  The row's bytes have been
@@ -127,7 +131,11 @@ __device__ __forceinline__ float div_full_weight(float x)
 // wave works them out while the others unpack); they are read from `smw` after the FFT, where ROLE 0 first needs
 // them, and what to request next (the same row again for its excised transform, else `after_row` of pol 1) is decided
 // there too.
-template <int ROLE, bool FIX = false, bool DEFER = false, bool COH = false>
+// INJ 0: no FRB injection code at all (k_channelize, k_channelize_kur: production runs without injection, and a
+// run-time test put a uniform branch, the booleans' re-materialisation and the injection parameters' registers into
+// every channel); INJ 1: the run-time test (the injecting twins k_inject_chan*, chosen by launch_channelize when
+// there is something to inject, and the coherence twins).
+template <int ROLE, bool FIX = false, bool DEFER = false, bool COH = false, int INJ = 1>
 __device__ __forceinline__ void channelize_pass(const ChanArgs &a, f2 *buf, int tid, int seg, int row, int pol, int ant,
                                                 RowStage &st, unsigned mask, float wrow, size_t prow, int next_row,
                                                 int next_pol = -1, bool prestaged = false,
@@ -201,13 +209,19 @@ __device__ __forceinline__ void channelize_pass(const ChanArgs &a, f2 *buf, int 
 #endif
 
     // FRB injection window of this row, per channel (inject_frb :361-380)
-    const bool inject = a.frb.delays != nullptr && a.inject_now > 0;
+    const bool inject = INJ && a.frb.delays != nullptr && a.inject_now > 0;
     const int since = inject ? (a.inject_now - 1 + seg) * a.R : 0;
     const bool also_kur = a.rfi_mode == 2 && ROLE == 0 && mask == 0;
     // the weight of a row without flags: 25 x 0.04f summed left to right = 1 + 2^-23
     const bool full_w = __builtin_bit_cast(unsigned, wrow) == 0x3f800001u;
     float *P0 = (ROLE == 1 ? a.Pkur : a.Praw) + prow;
     float *P1 = a.Pkur + prow;
+    // What is the same for the whole row is settled here, once, and handed to the four slices through registers the
+    // compiler cannot re-derive (left to itself it redid the 64-bit scalar adds of both row pointers and the two
+    // tests in every slice, 14 issue slots each time): the two planes' rows, and what the excised plane gets from
+    // this transform -- 0 nothing, 1 the powers over 1 + 2^-23 on the bits, 2 the powers over wrow.
+    int kur_how = also_kur ? (full_w ? 1 : 2) : 0;
+    if constexpr (!COH) asm volatile("" : "+s"(kur_how), "+s"(P0), "+s"(P1));
     // four consecutive channels per thread: 16-byte twiddle loads and 16-byte power stores (one
     // channel per lane would spare the 8-way LDS bank conflicts of these reads, but its 4-byte stores
     // measured 9 % slower overall)
@@ -241,23 +255,24 @@ __device__ __forceinline__ void channelize_pass(const ChanArgs &a, f2 *buf, int 
                 *(float2 *)(P0 + prow + 2 * (k - PB_CHANMIN)) = make_float2(X.x, X.y);
                 if (ROLE == 0 && also_kur) *(float2 *)(P1 + prow + 2 * (k - PB_CHANMIN)) = make_float2(X.x, X.y);
             } else {
+                // (one add into the value's place in the store quad: left to pair the four sums into packed adds,
+                //  the compiler spends more on moving the halves together than the pairing saves)
                 const f2 sq = X * X;
-                pw[q] = sq.x + sq.y;
+                asm("v_add_f32 %0, %1, %2" : "=v"(pw[q]) : "v"(sq.x), "v"(sq.y));
             }
         }
         if constexpr (COH) continue;
         // the excised plane carries pow / w (detect_and_normalize3 :452,:481), so that the
-        // serial bandpass recurrence downstream has no division in it
-        if (ROLE == 0) store_plane4(P0, c4, pw[0], pw[1], pw[2], pw[3]);
+        // serial bandpass recurrence downstream has no division in it.  (The rows' pointers have been through
+        // registers: the casts say again that they are global memory.  The thread's address is one 64-bit vector
+        // add per store; holding it, or a 32-bit offset beside scalar bases, across the slices cost registers the
+        // kernel does not have -- 8 to 24 bytes of scratch in every form tried.)
+        if (ROLE == 0) store_plane4((pb_gfloat *)(P0 + c4), pw[0], pw[1], pw[2], pw[3]);
         if (ROLE == 1)
-            store_plane4(P0, c4, pw[0] / wrow, pw[1] / wrow, pw[2] / wrow, pw[3] / wrow);
-        else if (also_kur)
-        {
-            if (full_w)
-                store_plane4(P1, c4, div_full_weight(pw[0]), div_full_weight(pw[1]), div_full_weight(pw[2]),
-                             div_full_weight(pw[3]));
-            else
-                store_plane4(P1, c4, pw[0] / wrow, pw[1] / wrow, pw[2] / wrow, pw[3] / wrow);
+            store_plane4((pb_gfloat *)(P0 + c4), pw[0] / wrow, pw[1] / wrow, pw[2] / wrow, pw[3] / wrow);
+        else if (kur_how) {
+            div_row_weight4(pw, wrow, kur_how == 1);
+            store_plane4((pb_gfloat *)(P1 + c4), pw[0], pw[1], pw[2], pw[3]);
         }
     }
 #ifdef FFT_LEAN
@@ -317,8 +332,16 @@ extern "C" int pb_internal_kur_stamps(unsigned long long *out)
 #define KSTAMP(i)
 #endif
 #define CH_COH 0
+#define CH_INJ 0
 #define CH_K_PLAIN k_channelize
 #define CH_K_KUR k_channelize_kur
+#include "k_channelize_kernels.inc"
+#undef CH_INJ
+#undef CH_K_PLAIN
+#undef CH_K_KUR
+#define CH_INJ 1
+#define CH_K_PLAIN k_inject_chan
+#define CH_K_KUR k_inject_chan_kur
 #include "k_channelize_kernels.inc"
 #undef CH_COH
 #undef CH_K_PLAIN
@@ -328,6 +351,7 @@ extern "C" int pb_internal_kur_stamps(unsigned long long *out)
 #define CH_K_KUR k_coh_chan_kur
 #include "k_channelize_kernels.inc"
 #undef CH_COH
+#undef CH_INJ
 #undef CH_K_PLAIN
 #undef CH_K_KUR
 
@@ -392,10 +416,13 @@ hipError_t launch_channelize(pb_handle *h, int nseg, int inject_now)
     a.wrow_out = b.d_wrow.p;
     a.rowmask_out = pb_rowmask(h);
     a.dag = h->d_dag.p;
+    // the power-plane kernels carry no injection code; their twins that do run only when there is a pulse to inject
+    const bool inject = inject_now > 0 && a.frb.delays != nullptr;
     if (pb_fused_kurtosis(h)) {
         // one workgroup per row (both pols): it computes the row's flags itself
         dim3 gk((unsigned)h->R, (unsigned)nseg, (unsigned)h->A);
         if (h->cfg.coherence) k_coh_chan_kur<<<gk, 256, 0, h->stream>>>(a);
+        else if (inject) k_inject_chan_kur<<<gk, 256, 0, h->stream>>>(a);
         else k_channelize_kur<<<gk, 256, 0, h->stream>>>(a);
         return hipGetLastError();
     }
@@ -406,10 +433,11 @@ hipError_t launch_channelize(pb_handle *h, int nseg, int inject_now)
     }
 #ifdef FFT_LEAN
     static const int lean_lds = pb_lean_lds(M_HALF * 8);
-    k_channelize<<<grid, 256, lean_lds, h->stream>>>(a);
 #else
-    k_channelize<<<grid, 256, 0, h->stream>>>(a);
+    const int lean_lds = 0;
 #endif
+    if (inject) k_inject_chan<<<grid, 256, lean_lds, h->stream>>>(a);
+    else k_channelize<<<grid, 256, lean_lds, h->stream>>>(a);
     return hipGetLastError();
 }
 

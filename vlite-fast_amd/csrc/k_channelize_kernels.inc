@@ -1,6 +1,8 @@
 // The two production channelisers, k_channelize and k_channelize_kur (k_channelize.hip), written once and
-// included twice: CH_COH 0 = power planes (the kernels named k_channelize, k_channelize_kur), CH_COH 1 = the
-// complex spectra of coherence output (k_coh_chan, k_coh_chan_kur).  CH_K_PLAIN / CH_K_KUR name the kernels.
+// included three times: CH_COH 0 = power planes -- CH_INJ 0 without any FRB injection code (the kernels named
+// k_channelize, k_channelize_kur), CH_INJ 1 with it (k_inject_chan, k_inject_chan_kur: launched only when a pulse is
+// to be injected) -- and CH_COH 1 = the complex spectra of coherence output (k_coh_chan, k_coh_chan_kur, CH_INJ 1).
+// CH_K_PLAIN / CH_K_KUR name the kernels.
 // The coherence twins keep the float2 of every channel until it is stored: within the 168 registers of three
 // workgroups per CU that spilled, so they are built for two (256 registers; the LDS would hold three).
 #define CH_WG_PER_CU (CH_COH ? 2 : 3)
@@ -47,7 +49,7 @@ __global__ __launch_bounds__(256, CH_WG_PER_CU) void CH_K_PLAIN(ChanArgs a)
         const bool second = a.rfi_mode == 1 || (a.rfi_mode == 2 && mask != 0);
         if (i) __syncthreads();   // the previous transform has finished reading buf
         if (a.rfi_mode != 1) {
-            channelize_pass<0, false, false, CH_COH>(a, buf, tid, seg, row, pol, ant, st, mask, wrow, prow,
+            channelize_pass<0, false, false, CH_COH, CH_INJ>(a, buf, tid, seg, row, pol, ant, st, mask, wrow, prow,
                                                      second && !all_bad ? row : after);
             if (!second) continue;
         }
@@ -66,7 +68,7 @@ __global__ __launch_bounds__(256, CH_WG_PER_CU) void CH_K_PLAIN(ChanArgs a)
             __syncthreads();   // the raw pass has finished reading buf
             asm volatile("" : "+v"(tid));   // no sharing of tid-derived addresses across the two passes
         }
-        channelize_pass<1, false, false, CH_COH>(a, buf, tid, seg, row, pol, ant, st, mask, wrow, prow, after);
+        channelize_pass<1, false, false, CH_COH, CH_INJ>(a, buf, tid, seg, row, pol, ant, st, mask, wrow, prow, after);
     }
 }
 
@@ -172,7 +174,7 @@ __global__ __launch_bounds__(256, CH_WG_PER_CU) void CH_K_KUR(ChanArgs a)
         if (a.rfi_mode != 1) {
             // what is requested while this transform is in its spectrum step -- the same row again for its excised
             // transform, else pol 1's row -- is decided inside, once the mask is known
-            channelize_pass<0, true, true, CH_COH>(a, buf, tid, seg, row, pol, ant, st, 0u, 0.f, prow, -1, 1, pol == 0, smw, after_row);
+            channelize_pass<0, true, true, CH_COH, CH_INJ>(a, buf, tid, seg, row, pol, ant, st, 0u, 0.f, prow, -1, 1, pol == 0, smw, after_row);
             mask = __builtin_amdgcn_readfirstlane(smw[0]);
             wrow = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(smw[1]));
         }
@@ -192,7 +194,7 @@ __global__ __launch_bounds__(256, CH_WG_PER_CU) void CH_K_KUR(ChanArgs a)
             asm volatile("" : "+v"(tid));   // no sharing of tid-derived addresses across the two passes
         }
         // (RFI mode 1, pol 0: the bytes the statistic staged are still where this transform expects them)
-        channelize_pass<1, true, false, CH_COH>(a, buf, tid, seg, row, pol, ant, st, mask, wrow, prow, after_row, 1,
+        channelize_pass<1, true, false, CH_COH, CH_INJ>(a, buf, tid, seg, row, pol, ant, st, mask, wrow, prow, after_row, 1,
                                  a.rfi_mode == 1 && pol == 0);
     }
 #ifdef KUR_STAMP

@@ -79,7 +79,9 @@ __device__ __forceinline__ unsigned row_mask(const PfbArgs &a, int ant, int rr)
 // contributing rows has a flagged block), ROLE 1 = excised spectrum.  The masks and the weight are scalar loads
 // requested at the top of the kernel; ROLE 0 first needs them after the FFT, so their latency and that of the
 // rows' bytes run side by side.
-template <int role>
+// INJ 0: no FRB injection code at all (k_channelize_pfb); INJ 1: the run-time test (k_inject_pfb, launched only when
+// there is a pulse to inject) -- as in k_channelize.hip.
+template <int role, int INJ>
 __device__ __forceinline__ void pfb_pass(const PfbArgs &a, uint8_t *lds, int tid, int grow, int seg, int row, int pol,
                                          int ant, const unsigned (&mask)[4], unsigned differ, float w, size_t prow)
 {
@@ -216,11 +218,16 @@ __device__ __forceinline__ void pfb_pass(const PfbArgs &a, uint8_t *lds, int tid
     };
     fft6250(v, buf, (const f2 *)a.tw2, (const f2 *)a.tw3, tid, load_tq);
 
-    const bool inject = a.frb.delays != nullptr && a.inject_now > 0;
+    const bool inject = INJ && a.frb.delays != nullptr && a.inject_now > 0;
     const int since = inject ? (a.inject_now - 1 + seg) * a.R : 0;
     const bool also_kur = a.rfi_mode == 2 && role == 0 && differ == 0;
     float *P0 = (role == 1 ? a.Pkur : a.Praw) + prow;
     float *P1 = a.Pkur + prow;
+    // settled once for the row and handed to the four slices through registers (k_channelize.hip): the planes' rows
+    // and what the excised plane gets from this transform -- 0 nothing, 1 the powers as they are (x / 1 = x: no
+    // division for a row whose window is complete and unflagged), 2 the powers over w
+    int kur_how = also_kur ? (w != 1.0f ? 2 : 1) : 0;
+    asm volatile("" : "+s"(kur_how), "+s"(P0), "+s"(P1));
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int c4 = tid * 4 + 1024 * i;
@@ -246,22 +253,27 @@ __device__ __forceinline__ void pfb_pass(const PfbArgs &a, uint8_t *lds, int tid
                 if (row >= lo && row <= hi) X = X * mk2(a.frb.amp, a.frb.amp);
             }
             const f2 sq = X * X;
-            pw[q] = sq.x + sq.y;
+            asm("v_add_f32 %0, %1, %2" : "=v"(pw[q]) : "v"(sq.x), "v"(sq.y));   // (k_channelize.hip)
         }
-        if (role == 0) store_plane4(P0, c4, pw[0], pw[1], pw[2], pw[3]);
-        if (role == 1 || (also_kur && w != 1.0f))
-            store_plane4(role == 1 ? P0 : P1, c4, pw[0] / w, pw[1] / w, pw[2] / w, pw[3] / w);
-        else if (also_kur)      // x / 1 = x: no division for a row whose window is complete and unflagged
-            store_plane4(P1, c4, pw[0], pw[1], pw[2], pw[3]);
+        if (role == 0) store_plane4((pb_gfloat *)(P0 + c4), pw[0], pw[1], pw[2], pw[3]);
+        if (role == 1)
+            store_plane4((pb_gfloat *)(P0 + c4), pw[0] / w, pw[1] / w, pw[2] / w, pw[3] / w);
+        else if (kur_how) {
+            if (__builtin_expect(kur_how == 2, 0)) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) pw[q] = pw[q] / w;
+            }
+            store_plane4((pb_gfloat *)(P1 + c4), pw[0], pw[1], pw[2], pw[3]);
+        }
     }
 }
 
 // One workgroup per (row, pol) does both transforms (the second only when some contributing block is flagged: 43 %
 // of rows on clean noise), as k_channelize does: a second grid of workgroups for the excised spectra spent a load
 // latency each on finding out that 57 % of them had nothing to do.
-__global__ __launch_bounds__(256, 3) void k_channelize_pfb(PfbArgs a)
+template <int INJ>
+__device__ __forceinline__ void pfb_rows(const PfbArgs &a, uint8_t *lds)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t lds[4 * PFB_ROW_LDS];   // 50 112 B, reused as the FFT buffer
     int tid = threadIdx.x;
     // grid (R, nseg * 2, A): no division to find the row.  Workgroups go to the 8 XCDs in turn, and an input row
     // is read by the workgroups of four consecutive output rows: give every XCD a contiguous eighth of the
@@ -289,7 +301,7 @@ __global__ __launch_bounds__(256, 3) void k_channelize_pfb(PfbArgs a)
         }
     }
     const size_t prow = (size_t)ant * a.p_ant_stride + (((size_t)seg * 2 + pol) * a.R + row) * PB_NCHANOUT;
-    if (a.rfi_mode != 1) pfb_pass<0>(a, lds, tid, grow, seg, row, pol, ant, mask, differ, w, prow);
+    if (a.rfi_mode != 1) pfb_pass<0, INJ>(a, lds, tid, grow, seg, row, pol, ant, mask, differ, w, prow);
     if (a.rfi_mode == 0 || (a.rfi_mode == 2 && differ == 0)) return;
     if (w == 0.f) {
         for (int c = tid; c < PB_NCHANOUT; c += 256) a.Pkur[prow + c] = __builtin_inff();
@@ -299,7 +311,18 @@ __global__ __launch_bounds__(256, 3) void k_channelize_pfb(PfbArgs a)
         __syncthreads();   // the raw pass has finished reading the FFT buffer
         asm volatile("" : "+v"(tid));   // no sharing of tid-derived addresses across the two passes
     }
-    pfb_pass<1>(a, lds, tid, grow, seg, row, pol, ant, mask, differ, w, prow);
+    pfb_pass<1, INJ>(a, lds, tid, grow, seg, row, pol, ant, mask, differ, w, prow);
+}
+__global__ __launch_bounds__(256, 3) void k_channelize_pfb(PfbArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[4 * PFB_ROW_LDS];   // 50 112 B, reused as the FFT buffer
+    pfb_rows<0>(a, lds);
+}
+// its twin with the injection code
+__global__ __launch_bounds__(256, 3) void k_inject_pfb(PfbArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[4 * PFB_ROW_LDS];
+    pfb_rows<1>(a, lds);
 }
 
 
@@ -401,7 +424,8 @@ hipError_t launch_channelize_pfb(pb_handle *h, int nseg, int inject_now)
     a.rfi_mode = h->cfg.rfi_mode;
     a.inject_now = inject_now;
     dim3 grid((unsigned)h->R, (unsigned)(nseg * 2), (unsigned)h->A);
-    k_channelize_pfb<<<grid, 256, 0, h->stream>>>(a);
+    if (inject_now > 0 && a.frb.delays != nullptr) k_inject_pfb<<<grid, 256, 0, h->stream>>>(a);
+    else k_channelize_pfb<<<grid, 256, 0, h->stream>>>(a);
     return hipGetLastError();
 }
 
