@@ -52,10 +52,13 @@ after = stamps()
 out = [a - b for a, b in zip(after, before)]
 rc = 0
 nl = max(1, out[3])
-names = {0: "A", int(os.environ.get("D2_WAVE_L", "5")): "L", 1: "B0", 2: "B1", 3: "B2", 9 - int(os.environ.get("D2_WAVE_L", "5")): "B3"}
+names = {0: "A", int(os.environ.get("D2_WAVE_L", "5")): "L", 1: "B0", 2: "B1", 3: "B2", 9 - int(os.environ.get("D2_WAVE_L", "5")): "B3",
+         6: "C0", 7: "C1"}          # C: the conversion waves (taps 1, RFI mode 2)
 nstep = 10 * 1024 // 32 + 2
 print("rc", rc, "steps", nstep, "launches", nl, "pipelined" if PIPE else "alone")
-for w in range(6):
+for w in range(8):
+    if not out[w * 4 + 3]:
+        continue
     work, wait, extra = out[w * 4] / nl, out[w * 4 + 1] / nl, out[w * 4 + 2] / nl
     print("wave %d %-3s work %8d (%6.0f/step)  barrier wait %8d (%6.0f/step)  dma wait %8d (%6.0f/step)"
           % (w, names.get(w, "?"), work, work / nstep, wait, wait / nstep, extra, extra / nstep))

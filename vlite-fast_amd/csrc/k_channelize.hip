@@ -14,9 +14,11 @@
 // r comes from 500-sample kurtosis block r, so a flagged block is simply a zeroed input.
 //
 // Passes (rfi_mode 2): every (row, pol) workgroup transforms the unflagged data and writes the raw
-// power plane -- and, when the row has no flagged block, the excised plane as well (same spectrum,
-// divided by the row weight).  Only when some block is flagged does it run a second pass on the
-// zeroed data (or write +inf, "no data", if every block is flagged).
+// power plane.  A row without a flagged block gets NOTHING in the excised plane: its excised power is
+// the raw power over the full weight 1 + 2^-23, which detect's excised stream derives from the raw
+// plane (k_detect2.hip, CONV == 2).  Only when some block is flagged does the workgroup run a second
+// pass on the zeroed data (or write +inf, "no data", if every block is flagged).  (The coherence twins
+// still store both planes for every row.)
 //
 // FRB injection (inject_frb): k_channelize and k_channelize_kur hold no injection code; launch_channelize picks their
 // twins k_inject_chan and k_inject_chan_kur, the same text with the per-channel window test compiled in, for the calls
@@ -29,7 +31,7 @@
 //
 // LDS: one 6250 x float2 buffer (50 000 B) used in place: every pass reads its inputs into
 // registers, barriers, then writes.  3 workgroups per CU.
-// HBM traffic per (row, pol): 12.5 KB of samples read, 16 KB + 16 KB of power written;
+// HBM traffic per (row, pol): 12.5 KB of samples read, 16 KB of power written (+ 16 KB for a row with flags);
 // twiddles (tw2 4.9 KB, tw3 49 KB, post 49 KB) stay in L2.
 #include <cstdlib>
 #include <cstring>
@@ -118,7 +120,7 @@ __device__ __forceinline__ void stage_request(const ChanArgs &a, int tid, int se
 // sixteen values: 13 slots per value, 11 of the true division's instructions not executed but 8 of masking added.
 #include "spectrum_div4.h"
 
-// One transform of one (row, pol): ROLE 0 = raw spectrum (also fills the excised plane when the row
+// One transform of one (row, pol): ROLE 0 = raw spectrum (the coherence twins: also the excised plane's when the row
 // has no flagged block), ROLE 1 = excised spectrum (flagged blocks zeroed).  The row's bytes have been
 // requested by stage_request; mask and wrow may still be in flight (ROLE 0 first needs them after the FFT).
 // next_row >= 0: the bytes of that row (of the same segment and pol) are requested into st as soon as the FFT is
@@ -219,8 +221,12 @@ __device__ __forceinline__ void channelize_pass(const ChanArgs &a, f2 *buf, int 
     // What is the same for the whole row is settled here, once, and handed to the four slices through registers the
     // compiler cannot re-derive (left to itself it redid the 64-bit scalar adds of both row pointers and the two
     // tests in every slice, 14 issue slots each time): the two planes' rows, and what the excised plane gets from
-    // this transform -- 0 nothing, 1 the powers over 1 + 2^-23 on the bits, 2 the powers over wrow.
-    int kur_how = also_kur ? (full_w ? 1 : 2) : 0;
+    // this transform -- 0 nothing, 2 the powers over wrow.  A row of the full weight (every row without flags) gets
+    // NOTHING: its excised power is a function of the raw plane, pow / (1 + 2^-23), and detect's excised stream takes it
+    // from there (k_detect2.hip, CONV == 2) -- the division and 16 KB of stores per (row, pol) less, for 83 - 87 % of rows.
+    // (1, the powers over 1 + 2^-23 on the bits, is what this kernel stored for such a row before; the rule lives on in
+    // spectrum_div4.h for detect.)
+    int kur_how = also_kur && !full_w ? 2 : 0;
     if constexpr (!COH) asm volatile("" : "+s"(kur_how), "+s"(P0), "+s"(P1));
     // four consecutive channels per thread: 16-byte twiddle loads and 16-byte power stores (one
     // channel per lane would spare the 8-way LDS bank conflicts of these reads, but its 4-byte stores

@@ -43,8 +43,8 @@ __global__ __launch_bounds__(256, CH_WG_PER_CU) void CH_K_PLAIN(ChanArgs a)
         const float wrow = __builtin_bit_cast(float, __builtin_amdgcn_readlane(vmw, CH_ROWS + i));
         const size_t prow = (size_t)ant * a.p_ant_stride + (((size_t)seg * 2 + pol) * a.R + row) * PB_NCHANOUT;
         const bool all_bad = mask == 0x1ffffffu;
-        // transforms of this row: role 0 = raw spectrum (also fills the excised plane when the row has no
-        // flagged block), role 1 = excised spectrum (only when some block is flagged: 13 % of rows on clean
+        // transforms of this row: role 0 = raw spectrum (an unflagged row's excised power is derived from it
+        // downstream), role 1 = excised spectrum (only when some block is flagged: 13 % of rows on clean
         // noise), instead of launching a second grid of workgroups of which 87 % would exit at once.
         const bool second = a.rfi_mode == 1 || (a.rfi_mode == 2 && mask != 0);
         if (i) __syncthreads();   // the previous transform has finished reading buf

@@ -67,7 +67,7 @@ struct PfbArgs {
 __device__ __forceinline__ unsigned row_mask(const PfbArgs &a, int ant, int rr)
 {
     // flags of the 25 blocks of row rr (rr < 0: history slot 3 + rr, the first three rows of a batch only)
-    if (rr >= 0) return __builtin_amdgcn_readfirstlane(a.rowmask[(size_t)ant * a.wrow_ant_stride + rr]);
+    if (rr >= 0) return __builtin_amdgcn_readfirstlane(a.rowmask[(size_t)ant * a.wrow_ant_stride + rr]) & PB_ROWMASK_FLAGS;
     const uint8_t *f = a.hflags + ((size_t)ant * 3 + (3 + rr)) * PB_BLK_PER_FFT;
     unsigned m = 0;
 #pragma unroll
@@ -76,14 +76,17 @@ __device__ __forceinline__ unsigned row_mask(const PfbArgs &a, int ant, int rr)
 }
 
 // One transform of one (row, pol): ROLE 0 = raw spectrum (also fills the excised plane when none of the four
-// contributing rows has a flagged block), ROLE 1 = excised spectrum.  The masks and the weight are scalar loads
+// contributing rows has a flagged block but one of them is absent, i.e. w < 1; kur_in_raw: the window is complete and
+// unflagged, the excised power is the raw power and is NOT stored a second time -- detect's excised stream reads the
+// raw plane for such a row, k_detect2.hip CONV == 1), ROLE 1 = excised spectrum.  The masks and the weight are scalar loads
 // requested at the top of the kernel; ROLE 0 first needs them after the FFT, so their latency and that of the
 // rows' bytes run side by side.
 // INJ 0: no FRB injection code at all (k_channelize_pfb); INJ 1: the run-time test (k_inject_pfb, launched only when
 // there is a pulse to inject) -- as in k_channelize.hip.
 template <int role, int INJ>
 __device__ __forceinline__ void pfb_pass(const PfbArgs &a, uint8_t *lds, int tid, int grow, int seg, int row, int pol,
-                                         int ant, const unsigned (&mask)[4], unsigned differ, float w, size_t prow)
+                                         int ant, const unsigned (&mask)[4], unsigned differ, float w, size_t prow,
+                                         bool kur_in_raw)
 {
     f2 *buf = (f2 *)lds;
     // window coefficients of samples (2n, 2n+1), n = tid + 250 r, tap j: through a buffer descriptor
@@ -220,12 +223,12 @@ __device__ __forceinline__ void pfb_pass(const PfbArgs &a, uint8_t *lds, int tid
 
     const bool inject = INJ && a.frb.delays != nullptr && a.inject_now > 0;
     const int since = inject ? (a.inject_now - 1 + seg) * a.R : 0;
-    const bool also_kur = a.rfi_mode == 2 && role == 0 && differ == 0;
+    const bool also_kur = a.rfi_mode == 2 && role == 0 && differ == 0 && !kur_in_raw;
     float *P0 = (role == 1 ? a.Pkur : a.Praw) + prow;
     float *P1 = a.Pkur + prow;
     // settled once for the row and handed to the four slices through registers (k_channelize.hip): the planes' rows
-    // and what the excised plane gets from this transform -- 0 nothing, 1 the powers as they are (x / 1 = x: no
-    // division for a row whose window is complete and unflagged), 2 the powers over w
+    // and what the excised plane gets from this transform -- 0 nothing (also for a complete, unflagged window:
+    // kur_in_raw), 1 the powers as they are (w = 1), 2 the powers over w
     int kur_how = also_kur ? (w != 1.0f ? 2 : 1) : 0;
     asm volatile("" : "+s"(kur_how), "+s"(P0), "+s"(P1));
 #pragma unroll
@@ -300,8 +303,11 @@ __device__ __forceinline__ void pfb_rows(const PfbArgs &a, uint8_t *lds)
             differ |= mask[j];
         }
     }
+    // (the word of mask[3], with the bit that k_pfb_weights added)
+    const bool kur_in_raw = a.rfi_mode == 2 &&
+        (__builtin_amdgcn_readfirstlane(a.rowmask[(size_t)ant * a.wrow_ant_stride + grow]) & PB_ROWMASK_KUR_IN_RAW) != 0;
     const size_t prow = (size_t)ant * a.p_ant_stride + (((size_t)seg * 2 + pol) * a.R + row) * PB_NCHANOUT;
-    if (a.rfi_mode != 1) pfb_pass<0, INJ>(a, lds, tid, grow, seg, row, pol, ant, mask, differ, w, prow);
+    if (a.rfi_mode != 1) pfb_pass<0, INJ>(a, lds, tid, grow, seg, row, pol, ant, mask, differ, w, prow, kur_in_raw);
     if (a.rfi_mode == 0 || (a.rfi_mode == 2 && differ == 0)) return;
     if (w == 0.f) {
         for (int c = tid; c < PB_NCHANOUT; c += 256) a.Pkur[prow + c] = __builtin_inff();
@@ -311,7 +317,7 @@ __device__ __forceinline__ void pfb_rows(const PfbArgs &a, uint8_t *lds)
         __syncthreads();   // the raw pass has finished reading the FFT buffer
         asm volatile("" : "+v"(tid));   // no sharing of tid-derived addresses across the two passes
     }
-    pfb_pass<1, INJ>(a, lds, tid, grow, seg, row, pol, ant, mask, differ, w, prow);
+    pfb_pass<1, INJ>(a, lds, tid, grow, seg, row, pol, ant, mask, differ, w, prow, false);
 }
 __global__ __launch_bounds__(256, 3) void k_channelize_pfb(PfbArgs a)
 {
@@ -327,7 +333,7 @@ __global__ __launch_bounds__(256, 3) void k_inject_pfb(PfbArgs a)
 
 
 // row weights of the PFB mode (see the header comment); overwrites wrow[g]
-__global__ void k_pfb_weights(const uint32_t *__restrict__ rowmask, size_t wrow_ant_stride,
+__global__ void k_pfb_weights(uint32_t *rowmask, size_t wrow_ant_stride,
                               const uint8_t *__restrict__ hflags, const float *__restrict__ tapE,
                               float *__restrict__ wrow, int nrows)
 {
@@ -342,7 +348,7 @@ __global__ void k_pfb_weights(const uint32_t *__restrict__ rowmask, size_t wrow_
     for (int j = 0; j < 4; ++j) {
         const int rr = g - 3 + j;
         if (rr >= 0) {
-            m[j] = rowmask[(size_t)ant * wrow_ant_stride + rr];
+            m[j] = rowmask[(size_t)ant * wrow_ant_stride + rr] & PB_ROWMASK_FLAGS;
         } else {
             const uint8_t *f = hflags + ((size_t)ant * 3 + (3 + rr)) * PB_BLK_PER_FFT;
             unsigned mm = 0;
@@ -361,6 +367,10 @@ __global__ void k_pfb_weights(const uint32_t *__restrict__ rowmask, size_t wrow_
                 if (!((m[j] >> b) & 1u)) s = s + tapE[j * PB_BLK_PER_FFT + b];
     }
     wrow[(size_t)ant * wrow_ant_stride + g] = s / tapE[100];
+    // A complete window without flags (an absent row counts as flagged here): the row's excised power is its raw power,
+    // and bit 31 of its mask word tells the channeliser and detect so (pb_internal.h).  The neighbouring rows' threads
+    // read this word too, but only its flag bits, which this store does not change.
+    if (!(m[0] | m[1] | m[2] | m[3])) rowmask[(size_t)ant * wrow_ant_stride + g] = m[3] | PB_ROWMASK_KUR_IN_RAW;
 }
 
 // keep the last three rows (and flags) of the batch for the next call

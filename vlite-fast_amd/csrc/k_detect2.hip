@@ -30,6 +30,17 @@
 // the serial path.  Stream, npol and nbit are template parameters and every data-dependent choice is a
 // select, so each phase is straight-line code.
 //
+// RFI mode 2: rows WITHOUT flags exist in the raw plane only (CONV below).  The channelisers no longer store their
+// copy in the excised plane (83 - 87 % of rows on noise: 16 KB x 2 pols each, ~285 of the 672 MB a launch wrote);
+// the excised stream's loader takes such a row from the raw plane instead -- the same LDS-DMA instructions, a per-lane
+// source select from one word of "row lives in the raw plane" bits per chunk, which the recurrence wave leaves in
+// LDS from what it loads for phase B anyway -- and, with the rectangular window, where that copy was
+// raw / (1 + 2^-23), two further waves (6, 7) apply exactly that to the chunk in its ring slot one step before the
+// recurrence reads it (div_row_weight4 of spectrum_div4.h, the header the channeliser used, checked over every
+// binary32 by tests/test_spectrum_div4_cpu.py).  The loader wave does no arithmetic: the first version of this
+// (profiles/r04_notes.md section 9) converted on the loader wave and doubled detect's time.  Rows of the excised plane
+// that are not written hold stale values of earlier batches; nothing reads them.
+//
 // Exactness notes (all selects reproduce the reference's branches bit for bit):
 //   (double)w >= 0.2  <=>  w >= 0.2f   (0.2f is the smallest float above 0.2);
 //   0.5*(w+w) == w exactly; adding +0.0f to a sum that started at +0.0f is the identity;
@@ -39,10 +50,12 @@
 #include <cstdlib>
 
 #include "pb_internal.h"
+#include "spectrum_div4.h"
 
 struct Detect2Args {
-    const float *P[2];       // per stream [A][S][2][R][4096]; stream 1 holds pow / w
+    const float *P[2];       // per stream [A][S][2][R][4096]; stream 1 holds pow / w (rows with flags only, CONV != 0)
     const float *wrow;       // [A][S*R] row weights after apply_kurtosis
+    const uint32_t *rowmask; // [A][S*R] flag masks; bit 31 (taps = 4): the row's excised power is its raw power
     float *bp;               // [A][2][2][4096]
     uint8_t *codes;          // [A][2][S][trim]
     float *ave;              // [A][2][S][ave_per_seg] or nullptr
@@ -75,7 +88,18 @@ struct Detect2Args {
 #define D2_NSLOT (DEPTH + 2)       // (4 x 8 KB + 16 KB of bp = 49 KB at DEPTH 2:
                                    // a detect workgroup fits beside two channeliser workgroups of the next batch)
 #define D2_THREADS 384
+#define D2_THREADS_CONV 512        // + the two conversion waves (CONV == 2)
 #define D2_WAVE_A 0
+#define D2_WAVE_C 6                // first of the two conversion waves
+// CONV (template parameter, excised stream): where rows without flags come from.
+//   0  the excised plane holds every row (RFI mode 1: there is no raw plane);
+//   1  from the raw plane as they are (taps = 4: an unflagged window has weight 1; bit 31 of the row's mask word says so);
+//   2  from the raw plane, divided by the full weight 1 + 2^-23 in LDS (taps = 1: the row's weight has those bits).
+// With CONV == 2 a chunk must have landed one step earlier (the conversion waves take chunk k+1 during step k), so of
+// the DEPTH chunks requested ahead DEPTH - 2 are still in flight at a step's barrier instead of DEPTH - 1; the ring keeps
+// its DEPTH + 2 slots (57 KB at DEPTH 3: tests/test_kernel_resources.py holds the kernel to 60 KB).
+#define D2_FULL_W_BITS 0x3f800001u // 25 x 0.04f summed left to right = 1 + 2^-23
+#define D2_NW (CONV ? 8 : 3)       // ring of row-weight chunks in LDS
 #ifndef D2_WAVE_L
 #define D2_WAVE_L 5               // waves i and i+4 share a SIMD
 #endif
@@ -285,10 +309,12 @@ template <int DEPTH> struct Cursor {
 
 }  // namespace
 
-template <int T, bool KUR, int NPOL, int NBIT, int DEPTH>
+template <int T, bool KUR, int NPOL, int NBIT, int DEPTH, int CONV>
 __device__ __forceinline__ void detect2_body(const Detect2Args &a, float (*s_p)[T][64], float4 (*s_u)[T / 4][64],
-                                             float (*s_u0)[64], float (*s_w)[T])
+                                             float (*s_u0)[64], float (*s_w)[T], unsigned *s_f)
 {
+    static_assert(CONV == 0 || KUR, "only the excised stream takes rows from the other plane");
+    static_assert(CONV != 2 || DEPTH >= 2, "a chunk lands one step before the recurrence reads it");
     // the wave index in a scalar register: every role test is a scalar branch, the step loops run on scalar counters
     // (Two detect workgroups per CU -- two antennas per handle -- already have their recurrence waves on different
     //  SIMDs: swapping waves 0 <-> 2 in the odd antennas' workgroups made detect 12 % slower alone, r05_notes.md.)
@@ -302,6 +328,10 @@ __device__ __forceinline__ void detect2_body(const Detect2Args &a, float (*s_p)[
     const float *wrow = a.wrow + (size_t)ant * a.S * R;
     const size_t pol_stride = (size_t)R * PB_NCHANOUT, seg_stride = 2 * pol_stride;
     const float *Pant = a.P[stream] + (size_t)ant * a.S * seg_stride;
+    const float *PantRaw = a.P[0] + (size_t)ant * a.S * seg_stride;       // (CONV != 0)
+    const uint32_t *rmask = a.rowmask + (size_t)ant * a.S * R;            // (CONV == 1)
+    constexpr int LEAD = CONV == 2 ? 1 : 0;      // steps between a chunk's landing and the recurrence
+    auto widx = [](int c) { return CONV ? (c & 7) : (c % 3); };
     constexpr int LPC = T / 4;        // DMA instructions per chunk (4 rows of 64 floats each)
     const int nstep = nchunk + 2;     // step k: loader k + D, A chunk k, B chunks k-1 (first half) and k-2 (second half)
     const int bi = b_index(wave);
@@ -318,7 +348,20 @@ __device__ __forceinline__ void detect2_body(const Detect2Args &a, float (*s_p)[
         const int ld_row = lane >> 4, ld_pol = (lane >> 3) & 1, ld_c = cg * 32 + (lane & 7) * 4;
         const size_t loff = (size_t)ld_pol * pol_stride + (size_t)ld_row * PB_NCHANOUT + ld_c;
         auto issue = [&](const Cursor<DEPTH> &cu) {
-            const float *src = Pant + (size_t)cu.seg * seg_stride + (size_t)(cu.rb * T) * PB_NCHANOUT + loff;
+            const size_t off = (size_t)cu.seg * seg_stride + (size_t)(cu.rb * T) * PB_NCHANOUT + loff;
+            const float *src = Pant + off;
+            if (CONV) {
+                // the lane's row of each group of four comes from the raw plane where its bit says so (the recurrence
+                // wave left the word in LDS at least one step ago)
+                const unsigned f = s_f[cu.c & 7] >> ld_row;
+                const float *srcR = PantRaw + off;
+#pragma unroll
+                for (int i = 0; i < LPC; ++i)
+                    __builtin_amdgcn_global_load_lds(
+                        (const void __attribute__((address_space(1))) *)(((f >> (4 * i)) & 1u ? srcR : src) + (size_t)(4 * i) * PB_NCHANOUT),
+                        (void __attribute__((address_space(3))) *)&s_p[cu.slot][4 * i][0], 16, 0, D2_LOAD_AUX);
+                return;
+            }
 #pragma unroll
             for (int i = 0; i < LPC; ++i)
                 __builtin_amdgcn_global_load_lds(
@@ -340,15 +383,17 @@ __device__ __forceinline__ void detect2_body(const Detect2Args &a, float (*s_p)[
                 cu.next(cps);
             }
         };
+        if (CONV) step_barrier();                    // the first chunks' source words are in LDS
         fill(DEPTH);
-        wait_chunks(cu.c - 1);                       // chunk 0 has landed
+        wait_chunks(cu.c - 1 - LEAD);                // chunk 0 (and 1) has landed
         step_barrier();
+        if (LEAD) step_barrier();                    // (chunk 0 is converted)
         for (int k = 0; k < nstep; ++k) {
             fill(k + 1 + DEPTH);
 #ifdef D2_STAMP
             const long long tw0 = D2_NOW();
 #endif
-            wait_chunks(cu.c - (k + 2));             // chunk k + 1 has landed
+            wait_chunks(cu.c - (k + 2 + LEAD));      // chunk k + 1 (+ LEAD) has landed
 #ifdef D2_STAMP
             clk.extra += D2_NOW() - tw0;
 #endif
@@ -365,14 +410,53 @@ __device__ __forceinline__ void detect2_body(const Detect2Args &a, float (*s_p)[
         // row weights of the next chunk are requested one step ahead (rows of chunk k are the contiguous
         // wrow[k*T .. k*T+T-1]) and staged in LDS for phase B
         auto ldw = [&](size_t i) { return wrow[i]; };
+        // does the row live in the raw plane?  (w: its weight, m: its mask word, CONV == 1 only)
+        auto in_raw = [&](float w, uint32_t m) {
+            return CONV == 2 ? __builtin_bit_cast(unsigned, w) == D2_FULL_W_BITS : (m & PB_ROWMASK_KUR_IN_RAW) != 0;
+        };
+        auto ldm = [&](size_t i) { return CONV == 1 ? rmask[i] : 0u; };
+        // CONV: the weights of chunk c go to the LDS ring DEPTH + 1 steps ahead of the recurrence, and with them one word
+        // of bits for the loader and the conversion waves: bit r = row r of the chunk comes from the raw plane
+        auto put = [&](int c, float w, uint32_t m) {
+            if (lane < T) s_w[c & 7][lane] = w;
+            const unsigned long long b = __ballot(lane < T && in_raw(w, m));
+            if (lane == 0) s_f[c & 7] = (unsigned)b;
+        };
         Cursor<DEPTH> cu;
         cu.init(0, cps);
+        float wv_next = 1.f;
+        uint32_t mv_next = 0u;
+        if (CONV) {
+            // the loader requests chunk k + DEPTH in step k: chunks 0 .. DEPTH before its first requests, then chunk
+            // k + DEPTH + 1 in step k (loaded one step earlier)
+            for (int c = 0; c <= DEPTH && c < nchunk; ++c)
+                put(c, lane < T ? ldw((size_t)c * T + lane) : 1.f, lane < T ? ldm((size_t)c * T + lane) : 0u);
+            if (DEPTH + 1 < nchunk && lane < T) {
+                wv_next = ldw((size_t)(DEPTH + 1) * T + lane);
+                mv_next = ldm((size_t)(DEPTH + 1) * T + lane);
+            }
+            step_barrier();
+        }
         step_barrier();
-        float wv_next = (KUR && lane < T && nchunk > 0) ? ldw(lane) : 1.f;
+        if (LEAD) step_barrier();
+        // bp's load is consumed HERE, before the loop.  Left pending into the loop, the compiler cannot tell on the back
+        // edge that it has long returned and waits for vmcnt(0) at bp's first use of every step -- straight after this
+        // step's request for the next chunk's weights, whose whole latency (~450 cycles of a 1 900-cycle step) the
+        // recurrence wave then sat out, step after step (profiles/r08_notes.md section 3).
+        asm volatile("" : "+v"(bp));
+        if (!CONV) wv_next = (KUR && lane < T && nchunk > 0) ? ldw(lane) : 1.f;
         for (int k = 0; k < nstep; ++k) {
+            if (CONV) {
+                const int c = k + DEPTH + 1;
+                if (c < nchunk) put(c, wv_next, mv_next);
+                if (c + 1 < nchunk && lane < T) {
+                    wv_next = ldw((size_t)(c + 1) * T + lane);
+                    mv_next = ldm((size_t)(c + 1) * T + lane);
+                }
+            }
             if (k < nchunk) {
                 const int slot = cu.slot, buf = k & 1;
-                if (KUR) {
+                if (KUR && !CONV) {
                     const float wv = wv_next;
                     if (k + 1 < nchunk && lane < T) wv_next = ldw((size_t)(k + 1) * T + lane);
                     if (lane < T) s_w[k % 3][lane] = wv;
@@ -387,10 +471,19 @@ __device__ __forceinline__ void detect2_body(const Detect2Args &a, float (*s_p)[
                         bp /= (float)R;
                     } else {
                         int good = 0;
+                        const float *praw = PantRaw + (size_t)polA * pol_stride + cA + (size_t)cu.seg * seg_stride;
                         for (int t = 0; t < R; ++t) {
-                            if (ldw(wseg + t) == 0.f) continue;
+                            const float w = ldw(wseg + t);
+                            if (w == 0.f) continue;
                             good++;
-                            bp += ldp(t);
+                            if (CONV && in_raw(w, ldm(wseg + t))) {
+                                // (a row without flags lives in the raw plane only; the division is what the bit rule of
+                                //  spectrum_div4.h reproduces)
+                                const float x = praw[(size_t)t * PB_NCHANOUT];
+                                bp += CONV == 2 ? x / __builtin_bit_cast(float, D2_FULL_W_BITS) : x;
+                            } else {
+                                bp += ldp(t);
+                            }
                         }
                         if (good == 0) bp = 1.f;
                         else bp /= (float)good;
@@ -501,7 +594,7 @@ __device__ __forceinline__ void detect2_body(const Detect2Args &a, float (*s_p)[
         Cursor<DEPTH> cu;                // this wave's next chunk: those of its parity
         cu.init(0, cps);
         if (par) cu.next(cps);
-        step_barrier();
+        for (int i = 0; i < 1 + (CONV ? 1 : 0) + LEAD; ++i) step_barrier();
         for (int k = 0; k < nstep; ++k) {
             // step k: chunk k-1 was finished by A in step k-1.  If it is ours: take it into registers and do
             // rows 0-3; otherwise finish the chunk taken in the previous step (rows 4-7, quantiser)
@@ -519,7 +612,7 @@ __device__ __forceinline__ void detect2_body(const Detect2Args &a, float (*s_p)[
                         bs.uprev[pol] = g == 0 ? s_u0[ub][pol * 32 + ch] : s_u[ub][(g ? 2 * g : 1) - 1][pol * 32 + ch].w;
                     }
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) bs.w[j] = KUR ? s_w[c1 % 3][g * 8 + j] : 1.f;
+                    for (int j = 0; j < 8; ++j) bs.w[j] = KUR ? s_w[widx(c1)][g * 8 + j] : 1.f;
                     bs.trow = cu.rb * NG + g;
                     bs.seg = cu.seg;
                     phase_b_rows<NPOL, KUR>(bs, 0);
@@ -534,8 +627,42 @@ __device__ __forceinline__ void detect2_body(const Detect2Args &a, float (*s_p)[
             }
             step_barrier();
         }
-    } else {
+    } else if (CONV == 2 && wave >= D2_WAVE_C) {
+        // ---- conversion: chunk k + 1, in place in its ring slot, during step k.  Two waves; a wave takes every other
+        // group of four rows (the groups of the loader's DMA instructions), lane -> (row of the group, 4 channels of a pol)
+        const int cw = wave - D2_WAVE_C, rq = lane >> 4, c4 = (lane & 15) * 4;
+        Cursor<DEPTH> cv;
+        cv.init(0, cps);
+        auto convert = [&]() {
+#ifndef D2_KFR_BOUND       // (variant builds, RESULTS INVALID: the rows unconverted -- what the step would be if this were free)
+            if (cv.c < nchunk) {
+                const unsigned f = s_f[cv.c & 7] >> rq;
+                constexpr int NI = (NQ + 1) / 2;
+                float4 v[NI];
+#pragma unroll
+                for (int i = 0; i < NI; ++i) v[i] = *(const float4 *)&s_p[cv.slot][4 * (2 * i + cw) + rq][c4];
+#pragma unroll
+                for (int i = 0; i < NI; ++i) {
+                    if ((f >> (4 * (2 * i + cw))) & 1u) {
+                        float x[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
+                        div_row_weight4(x, __builtin_bit_cast(float, D2_FULL_W_BITS), true);
+                        *(float4 *)&s_p[cv.slot][4 * (2 * i + cw) + rq][c4] = make_float4(x[0], x[1], x[2], x[3]);
+                    }
+                }
+            }
+#endif
+            cv.next(cps);
+        };
         step_barrier();
+        step_barrier();
+        convert();                                   // chunk 0
+        step_barrier();
+        for (int k = 0; k < nstep; ++k) {
+            convert();
+            step_barrier();
+        }
+    } else {
+        for (int i = 0; i < 1 + (CONV ? 1 : 0) + LEAD; ++i) step_barrier();
         for (int k = 0; k < nstep; ++k) step_barrier();
     }
 #ifdef D2_STAMP
@@ -561,39 +688,46 @@ __device__ __forceinline__ void detect2_body(const Detect2Args &a, float (*s_p)[
 }
 
 // MODE = rfi_mode: 0 raw stream only, 1 excised only, 2 both (blockIdx.y picks the stream)
-template <int T, int NPOL, int NBIT, int MODE, int DEPTH>
-__global__ __launch_bounds__(D2_THREADS) void k_detect2(Detect2Args a)
+template <int T, int NPOL, int NBIT, int MODE, int DEPTH, int CONV>
+__global__ __launch_bounds__(CONV == 2 ? D2_THREADS_CONV : D2_THREADS) void k_detect2(Detect2Args a)
 {
+    static_assert(CONV == 0 || MODE == 2, "rows come from the raw plane only where there is one");
     // ring of power chunks filled by LDS-DMA (global_load_lds_dwordx4: no registers, no VALU)
     __shared__ __attribute__((aligned(16))) float s_p[D2_NSLOT][T][64];
     // bp after each row, double-buffered per chunk: [row quad][column = (pol, channel)], four rows to a 16-byte
     // entry; s_u0 = bp before the chunk's first row
     __shared__ __attribute__((aligned(16))) float4 s_u[2][T / 4][64];
     __shared__ float s_u0[2][64];
-    __shared__ float s_w[3][T];
-    if (MODE == 0 || (MODE == 2 && blockIdx.y == 0)) detect2_body<T, false, NPOL, NBIT, DEPTH>(a, s_p, s_u, s_u0, s_w);
-    else detect2_body<T, true, NPOL, NBIT, DEPTH>(a, s_p, s_u, s_u0, s_w);
+    // row weights of the chunks between the loader's request and phase B, and (CONV) per chunk one word of "row comes
+    // from the raw plane" bits
+    __shared__ float s_w[D2_NW][T];
+    __shared__ unsigned s_f[8];
+    // (the raw stream's workgroups of a CONV == 2 launch have two idle waves: one block size per launch)
+    if (MODE == 0 || (MODE == 2 && blockIdx.y == 0)) detect2_body<T, false, NPOL, NBIT, DEPTH, 0>(a, s_p, s_u, s_u0, s_w, s_f);
+    else detect2_body<T, true, NPOL, NBIT, DEPTH, CONV>(a, s_p, s_u, s_u0, s_w, s_f);
 }
 
+// conv: CONV of the excised stream (mode 2 only)
 template <int T, int NPOL, int NBIT, int DEPTH>
-static void launch_mode(const Detect2Args &a, int mode, dim3 grid, hipStream_t st)
+static void launch_mode(const Detect2Args &a, int mode, int conv, dim3 grid, hipStream_t st)
 {
-    if (mode == 0) k_detect2<T, NPOL, NBIT, 0, DEPTH><<<grid, D2_THREADS, 0, st>>>(a);
-    else if (mode == 1) k_detect2<T, NPOL, NBIT, 1, DEPTH><<<grid, D2_THREADS, 0, st>>>(a);
-    else k_detect2<T, NPOL, NBIT, 2, DEPTH><<<grid, D2_THREADS, 0, st>>>(a);
+    if (mode == 0) k_detect2<T, NPOL, NBIT, 0, DEPTH, 0><<<grid, D2_THREADS, 0, st>>>(a);
+    else if (mode == 1) k_detect2<T, NPOL, NBIT, 1, DEPTH, 0><<<grid, D2_THREADS, 0, st>>>(a);
+    else if (conv == 1) k_detect2<T, NPOL, NBIT, 2, DEPTH, 1><<<grid, D2_THREADS, 0, st>>>(a);
+    else k_detect2<T, NPOL, NBIT, 2, DEPTH, 2><<<grid, D2_THREADS_CONV, 0, st>>>(a);
 }
 
 template <int T, int DEPTH>
-static void launch_all(const Detect2Args &a, int mode, int npol, int nbit, dim3 grid, hipStream_t st)
+static void launch_all(const Detect2Args &a, int mode, int conv, int npol, int nbit, dim3 grid, hipStream_t st)
 {
     if (npol == 1) {
-        if (nbit == 8) launch_mode<T, 1, 8, DEPTH>(a, mode, grid, st);
-        else if (nbit == 4) launch_mode<T, 1, 4, DEPTH>(a, mode, grid, st);
-        else launch_mode<T, 1, 2, DEPTH>(a, mode, grid, st);
+        if (nbit == 8) launch_mode<T, 1, 8, DEPTH>(a, mode, conv, grid, st);
+        else if (nbit == 4) launch_mode<T, 1, 4, DEPTH>(a, mode, conv, grid, st);
+        else launch_mode<T, 1, 2, DEPTH>(a, mode, conv, grid, st);
     } else {
-        if (nbit == 8) launch_mode<T, 2, 8, DEPTH>(a, mode, grid, st);
-        else if (nbit == 4) launch_mode<T, 2, 4, DEPTH>(a, mode, grid, st);
-        else launch_mode<T, 2, 2, DEPTH>(a, mode, grid, st);
+        if (nbit == 8) launch_mode<T, 2, 8, DEPTH>(a, mode, conv, grid, st);
+        else if (nbit == 4) launch_mode<T, 2, 4, DEPTH>(a, mode, conv, grid, st);
+        else launch_mode<T, 2, 2, DEPTH>(a, mode, conv, grid, st);
     }
 }
 
@@ -604,6 +738,7 @@ hipError_t launch_detect_pow(pb_handle *h, int nseg)
     a.P[0] = b.d_Praw.p;
     a.P[1] = b.d_Pkur.p;
     a.wrow = b.d_wrow.p;
+    a.rowmask = pb_rowmask(h);
     a.bp = h->d_bp.p;
     a.codes = b.d_codes.p;
     a.ave = h->cfg.keep_ave ? b.d_ave.p : nullptr;
@@ -628,11 +763,13 @@ hipError_t launch_detect_pow(pb_handle *h, int nseg)
     const int depth_env = h->sched.detect_depth;     // PB_DETECT_DEPTH 2 / 3: timing experiments
     const bool deep = depth_env ? depth_env == 3
                                 : (D2_DEPTH_OVERLAPPED == 3 && pb_fused_kurtosis(h) && h->cfg.taps == 1 && h->sets.size() >= 2 && h->A == 1);
+    // mode 2: the channelisers (k_channelize.hip, k_channelize_pfb.hip) leave rows without flags out of the excised plane
+    const int conv = h->cfg.rfi_mode == 2 ? (h->cfg.taps == 4 ? 1 : 2) : 0;
     if (h->R % 32 == 0) {
-        if (deep) launch_all<32, 3>(a, h->cfg.rfi_mode, h->cfg.npol, h->cfg.nbit, grid, h->stream);
-        else launch_all<32, 2>(a, h->cfg.rfi_mode, h->cfg.npol, h->cfg.nbit, grid, h->stream);
+        if (deep) launch_all<32, 3>(a, h->cfg.rfi_mode, conv, h->cfg.npol, h->cfg.nbit, grid, h->stream);
+        else launch_all<32, 2>(a, h->cfg.rfi_mode, conv, h->cfg.npol, h->cfg.nbit, grid, h->stream);
     } else {
-        launch_all<8, 2>(a, h->cfg.rfi_mode, h->cfg.npol, h->cfg.nbit, grid, h->stream);
+        launch_all<8, 2>(a, h->cfg.rfi_mode, conv, h->cfg.npol, h->cfg.nbit, grid, h->stream);
     }
     return hipGetLastError();
 }

@@ -234,7 +234,12 @@ bool pb_fused_kurtosis(const pb_handle *h);
 #ifndef PB_EXPERIMENTS
 #define PB_EXPERIMENTS 0
 #endif
-// row flag masks (bit r = kurtosis block r of the row is flagged), written by k_kurtosis_row behind the weights
+// row flag masks (bit r = kurtosis block r of the row is flagged), written by k_kurtosis_row behind the weights.
+// taps = 4 adds bit 31 (k_pfb_weights): the row's window is complete and has no flag, so its excised power IS its raw
+// power -- k_channelize_pfb then writes it to the raw plane only and detect's excised stream takes it from there.  (The
+// weight cannot say so: flagging the faintest block of the window alone, E / total = 2e-9, still rounds to 1.0f.)
+#define PB_ROWMASK_FLAGS 0x1ffffffu
+#define PB_ROWMASK_KUR_IN_RAW 0x80000000u
 static inline uint32_t *pb_rowmask(pb_handle *h) { return (uint32_t *)(h->set().d_wrow.p + (size_t)h->A * h->S * h->R); }
 
 // ---- launchers (each enqueues on h->stream and returns a hipError_t) ----
