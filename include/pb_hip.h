@@ -1037,6 +1037,59 @@ int pb_search_subband_dm(pb_search *s, int dmi, uint32_t *sub, float *band_snr, 
  * of the boxcars and the best band (each added up over the chunks), and of everything with the copy to the host */
 int pb_search_subband_timers(const pb_search *s, float *ms4);
 
+/* Periodicity search: trains of pulses that are each below the single-pulse threshold.  Every trial DM's series of the
+ * block that the last search left on the device is folded at every trial period by the fast folding algorithm (FFA) and
+ * each folded profile is searched with circular boxcars.  The definition is THIS project's own; parity with no pulsar
+ * package is claimed.  Off until pb_search_set_periodic; a pb_search on which it was never called allocates nothing more,
+ * launches nothing more and returns what it returns without it, byte for byte.
+ * Inputs: the series D[dm][0 .. tout) and rms = stats[dm][1] of the last pb_search_run / pb_search_peaks / pb_search_gulp_*.
+ * Parameters: B = bins in {32, 64, 128} -- a profile has p bins, B <= p < 2B -- and the octaves k_lo <= k <= k_hi,
+ * 0 <= k_lo <= k_hi <= 12.  For each (dm, k):
+ *   1. Downsampling.  x_k[j] = sum over u < 2^k of D[dm][j 2^k + u], j in [0, n_k), n_k = floor(tout / 2^k).  Exact.
+ *   For each base period p in [B, 2B):
+ *   2. Rows.  m = floor(n_k / p).  If m < 2 the base period is skipped.  M is the smallest power of two >= m, L = log2 M.
+ *      Row r of stage 0 is x_k[r p .. r p + p) for r < m and zeros for m <= r < M; the samples from m p on are not used.
+ *   3. Folding.  At stage s + 1 block b has 2^(s+1) trials, made from block 2b (head H) and block 2b + 1 (tail T) of stage
+ *      s: trial i uses h = i >> 1 and sh = (i + 1) >> 1, out[i][j] = H[h][j] + T[h][(j + sh) mod p].  After L stages there
+ *      are M profiles F[i][0 .. p); trial i stands for the period (p + i / (M - 1)) 2^k tsamp seconds.  In closed form
+ *      F[i][j] = sum over r < m of x_k[r p + ((j + s_L(r, i)) mod p)] with s_0 = 0, s_L(r, i) = s_{L-1}(r, i >> 1) for
+ *      r < 2^(L-1) and ((i + 1) >> 1) + s_{L-1}(r - 2^(L-1), i >> 1) otherwise: every bin is the sum of exactly m samples
+ *      of x_k.
+ *   4. Range.  Profiles are uint32: pb_search_set_periodic fails unless 255 nact ceil(max_samples / B) < 2^32.  Window
+ *      sums and the profile total are 64-bit.
+ *   5. Matched filter.  Widths w = 2^q, q = 0 .. Q, 2^Q = B / 2 (so w <= p / 2).  T = sum over j of F[i][j] (the same for
+ *      every i).  S(j, w) = sum over u < w of F[i][(j + u) mod p]: the window is circular.  Smax_q = max over j of
+ *      S(j, 2^q), j_q the smallest j that reaches it.  The S/N of (i, q) is evaluated in double and rounded once to
+ *      binary32: (double)(p Smax_q - w T), an exact integer, over (double)rms * sqrt((double)(m 2^k) * w * (p - w) * p).
+ *      The profile's own mean is removed; the noise is the series' clipped rms scaled to a sum of m 2^k w samples, with
+ *      the factor 1 - w / p for the mean that was removed.  Where rms is not above 0 the S/N is 0.
+ *   6. Best.  A trial's S/N is the largest over q, of equal values the smaller q; a base period's best trial is the largest
+ *      over i, of equal values the smaller i.  Comparisons are made in binary32.
+ *   7. DM chunks.  The trial DMs are processed dm_chunk at a time so that the two scratch buffers of [dm_chunk][sum over p
+ *      of M p] uint32 stay bounded (sum over p of M p < 2 n_k B): dm_chunk = 0 means what keeps them within 1 GiB, at least
+ *      1; any value is cut to ndm and to 65535.  Results do not depend on dm_chunk.
+ * Limits.  The series are not detrended: a slow baseline leaks into the longest periods.  There is no acceleration search
+ * and no harmonic summing: the boxcars over the folded profile are the matched filter.
+ * tests/search_periodic_ref.py restates all of it; tests/test_gpu_search_periodic.py holds the kernels to it (profiles and
+ * window positions exactly, the S/N to 1 binary32 ulp).
+ * pb_search_set_periodic allocates the buffers; bins = 0 frees them and switches the stage off.  PB_EINVAL with nothing
+ * changed (pb_search_last_error says why) for bins not 0, 32, 64 or 128, a bad octave range, dm_chunk < 0 or the range
+ * condition of 4. */
+int pb_search_set_periodic(pb_search *s, int bins, int k_lo, int k_hi, int dm_chunk);
+/* The best trial of every (dm, k, p) of the last block searched: best (host) is [ndm][k_hi - k_lo + 1][bins][4] int32 --
+ * S/N bits, i, q, j_q -- the entry of p at index p - bins; a skipped base period has the bits of 0.0f, i = -1, q = j = 0.
+ * PB_EINVAL with a message when the stage is off, no block has been searched or the pointer is missing. */
+int pb_search_periodic(pb_search *s, int32_t *best);
+/* One (dm, k, p) in full, for tests and for the profile of a candidate: *m and *M, and for M >= 2 prof [M][p] the folded
+ * profiles, snr [M][Q + 1] and jbest [M][Q + 1] the S/N and j_q of every (i, q).  Any pointer may be NULL; with prof, snr
+ * and jbest all NULL nothing is launched (the sizes only).  A skipped base period returns *m < 2, *M = 0 and writes nothing
+ * else.  PB_EINVAL as above, and for dmi outside [0, ndm), k outside
+ * [k_lo, k_hi] or p outside [bins, 2 bins). */
+int pb_search_periodic_fold(pb_search *s, int dmi, int k, int p, uint32_t *prof, float *snr, int32_t *jbest, int *m, int *M);
+/* the last pb_search_periodic: device time in ms of the folding (downsampling and stages, added up over the passes and
+ * octaves), of the last stage with the evaluation, and of everything with the copy to the host */
+int pb_search_periodic_timers(const pb_search *s, float *ms3);
+
 /* Page-locked host memory for the blocks handed to pb_submit_vdif(_at) (H2D copies from pageable memory are
  * staged and synchronous); the reference allocates its 1-s host buffer the same way (cudaMallocHost,
  * src/process_baseband.cu:579).  A host program above this ABI needs no HIP headers.  NULL on failure. */

@@ -1,5 +1,5 @@
 """Candidates on the host: the search's points, giants and sub-band points grouped into candidates (overlap .. subband_list,
-below the TCP leg), and candidates to the coincidencer: the TCP leg heimdall's `-coincidencer host:port` plays in the reference
+below the TCP leg), the periodicity search's best table grouped by harmonic ratio (periodic_octaves .. candidates_from_periodic), and candidates to the coincidencer: the TCP leg heimdall's `-coincidencer host:port` plays in the reference
 (scripts/start_heimdall_single_antenna:21 `-coincidencer vlite-nrl:27555`; server side
 /root/reference/src/trigger.py:7-8,37-43,84-123).
 
@@ -155,3 +155,79 @@ def candidates_from_subbands(res, dms, tsamp, bands, nsb, fch1, foff, nchan, sam
         edges = [fch1 + (first * per - 0.5) * foff, fch1 + ((first + count) * per - 0.5) * foff]
         c.update(band=(int(first), int(count)), f_lo=float(min(edges)), f_hi=float(max(edges)), snr_full=float(res["snr_full"][i]))
     return cands
+
+
+PERIODIC_BINS = (32, 64, 128)
+PERIODIC_K_MAX = 12            # the longest octave of the periodicity search (include/pb_hip.h, pb_search_set_periodic)
+
+
+def periodic_octaves(p_lo, p_hi, bins, tsamp):
+    """the octaves (k_lo, k_hi) whose periods bins 2^k tsamp .. 2 bins 2^k tsamp cover [p_lo, p_hi] seconds as far as the
+    search reaches: k_lo = max(0, floor(log2(p_lo / (bins tsamp)))), k_hi = floor(log2(p_hi / (bins tsamp))).  ValueError,
+    naming the bound, where p_hi is below the shortest searchable period or p_hi's octave is beyond the longest one."""
+    base = bins * tsamp
+    if not (p_lo > 0 and p_hi >= p_lo):
+        raise ValueError("periodic: need 0 < P_LO <= P_HI")
+    if p_hi < base:
+        raise ValueError("periodic: P_HI %g s is below the shortest searchable period, %g s (bins x tsamp)" % (p_hi, base))
+    k_lo = max(0, int(np.floor(np.log2(p_lo / base))))
+    k_hi = int(np.floor(np.log2(p_hi / base)))
+    if k_hi > PERIODIC_K_MAX:
+        raise ValueError("periodic: P_HI %g s is beyond the longest searchable period, %g s (2 bins x 2^%d tsamp)"
+                         % (p_hi, 2 * base * 2 ** PERIODIC_K_MAX, PERIODIC_K_MAX))
+    return min(k_lo, k_hi), k_hi
+
+
+def harmonic_ratio(period, period_c, tol, nmax=8):
+    """the ratio (a, b), a and b in 1..nmax in lowest terms, smallest a + b first, with |period b / (period_c a) - 1| <= tol
+    -- period is a / b of period_c within tol --, or None"""
+    best = None
+    for a in range(1, nmax + 1):
+        for b in range(1, nmax + 1):
+            if np.gcd(a, b) == 1 and abs(period * b / (period_c * a) - 1.0) <= tol and (best is None or a + b < sum(best)):
+                best = (a, b)
+    return best
+
+
+def candidates_from_periodic(res, dms, tsamp, thresh, max_cands=64, p_range=None):
+    """Searcher.periodic's best table as periodicity candidates.  The entries at or above thresh (with p_range = (lo, hi)
+    only those whose period lies in it), strongest first (ties: the smaller DM index, octave, base period); a weaker entry is
+    absorbed by a stronger kept candidate c when its period P is a small-integer ratio of c's, at any DM:
+    |P b / (P_c a) - 1| <= (w_c + 1) / (m_c p_c) for some a, b in 1..8 -- a period error drifts m times per fold and a pulse
+    survives a drift of about its own width.  At most max_cands are kept; what comes after them is dropped.  Each dict:
+    snr, period_s, dm, dmi, k, p, i, q, j, m, M, width_s = 2^q 2^k tsamp, phase = j / p, nabsorbed, and nharm = "a/b", the
+    ratio (harmonic_ratio) of the strongest absorbed entry's period to the candidate's ("1/1" with none absorbed)."""
+    snr = np.asarray(res["snr"], np.float32)
+    ok = (snr >= np.float32(thresh)) & (np.asarray(res["i"]) >= 0)
+    if p_range is not None:
+        with np.errstate(invalid="ignore"):
+            ok &= (res["period_s"] >= p_range[0]) & (res["period_s"] <= p_range[1])
+    idx = np.argwhere(ok)
+    order = np.argsort(-snr[ok].astype(np.float64), kind="stable")      # (argwhere ascends in dmi, octave, base period)
+    idx = idx[order]
+    per = np.array([res["period_s"][tuple(e)] for e in idx], np.float64)
+    live = np.ones(len(idx), bool)
+    ab = [(a, b) for a in range(1, 9) for b in range(1, 9)]
+    out = []
+    for n, e in enumerate(idx):
+        if not live[n]:
+            continue
+        if len(out) >= max_cands:
+            break
+        d, ki, pi = [int(v) for v in e]
+        k, p, q = int(res["octaves"][ki]), int(res["p"][pi]), int(res["q"][d, ki, pi])
+        m = int(res["m"][d, ki, pi])
+        tol = ((1 << q) + 1.0) / (m * p)
+        live[n] = False
+        hit = np.zeros(len(idx), bool)
+        for a, b in ab:
+            hit |= np.abs(per * b / (per[n] * a) - 1.0) <= tol
+        hit &= live
+        live &= ~hit
+        first = np.nonzero(hit)[0]
+        ratio = (harmonic_ratio(per[first[0]], per[n], tol) if first.size else None) or (1, 1)
+        out.append(dict(snr=float(snr[d, ki, pi]), period_s=float(per[n]), dm=float(dms[d]), dmi=d, k=k, p=p,
+                        i=int(res["i"][d, ki, pi]), q=q, j=int(res["j"][d, ki, pi]), m=m, M=int(res["M"][d, ki, pi]),
+                        width_s=float((1 << q) * (1 << k) * tsamp), phase=float(res["j"][d, ki, pi]) / p,
+                        nabsorbed=int(hit.sum()), nharm="%d/%d" % ratio))
+    return out

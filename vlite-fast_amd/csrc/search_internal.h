@@ -1,6 +1,6 @@
 // What the search's translation units share on the host side: the handle, the dispersion delay, the error and timer
 // helpers, and each stage's free function.  search_run.hip holds the core (create .. fetch_clean) and the RFI cleaning, search_rfichan.hip the cleaning's channel stage;
-// search_cutout.hip, search_refine.hip, search_giants.hip, search_stream.hip, search_pol.hip and search_subband.hip one optional stage each, kernels and host side together (a
+// search_cutout.hip, search_refine.hip, search_giants.hip, search_stream.hip, search_pol.hip, search_subband.hip and search_periodic.hip one optional stage each, kernels and host side together (a
 // kernel lives in the file that launches it); search_plane.hip the streaming stage's entry for fp32 planes.  Device-only helpers: search_dev.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -157,6 +157,22 @@ struct pb_search {
         std::vector<hipEvent_t> ev;        // per pass: start, dedispersed, statistics; then kernels done, copy done
         float ms[4] = {};                  // last pb_search_subbands: dedispersion, sums + statistics, boxcars + best, all with the copy
     } sub;
+    // periodicity search (pb_search_set_periodic); the buffers exist while it is switched on (bins > 0)
+    struct {
+        int bins = 0, k_lo = 0, k_hi = 0, Q = 0;           // base periods bins .. 2 bins - 1, octaves, widths 2^0 .. 2^Q = bins / 2
+        int chunk = 0;                     // trial DMs per pass of the stage's kernels
+        size_t spitch = 0;                 // words of a scratch row: one trial DM, one octave, every base period's M rows
+        uint32_t *d_buf[2] = {};           // [chunk][spitch] the folding stages, written in turn
+        int32_t *d_tab = nullptr;          // [nk][bins][4] per octave and base period: offset in the scratch row, m, L, M
+        std::vector<int32_t> h_tab;        // the same on the host
+        int tab_tout = 0;                  // tout that the tables were made for
+        int32_t *d_best = nullptr;         // [ndm][nk][bins][4] S/N bits, i, q, j
+        uint32_t *d_fprof = nullptr;       // pb_search_periodic_fold: [M][p] profiles
+        float *d_fsnr = nullptr;           // [M][Q + 1] S/N
+        int32_t *d_fj = nullptr;           // [M][Q + 1] first bin of the best window
+        std::vector<hipEvent_t> ev;        // per pass and octave: start, folded; then kernels done, copy done
+        float ms[3] = {};                  // last pb_search_periodic: folding, evaluation, everything with the copy
+    } per;
 };
 
 // The dispersion delay of one channel in samples, in double: 4.148808e3 MHz^2 s (src/candidate.py:33) x DM x
@@ -230,6 +246,7 @@ SEARCH_LOCAL void search_giants_free(pb_search *s);
 SEARCH_LOCAL void search_gulp_free(pb_search *s);
 SEARCH_LOCAL void search_pol_free(pb_search *s);
 SEARCH_LOCAL void search_subbands_free(pb_search *s);
+SEARCH_LOCAL void search_periodic_free(pb_search *s);
 
 // search_rfichan.hip, for search_run.hip: the channel stage on the nsamp samples of d_xt, in place
 SEARCH_LOCAL int search_rfichan_launch(pb_search *s, int nsamp);

@@ -583,6 +583,7 @@ extern "C" void pb_search_destroy(pb_search *s)
     search_gulp_free(s);
     search_pol_free(s);
     search_subbands_free(s);
+    search_periodic_free(s);
     search_release({s->d_codes, s->d_xt, s->d_delay, s->d_D, s->d_stats, s->d_snr, s->d_wid, s->d_P, s->d_peaks, s->d_chans},
                    nullptr, s->ev, 7);
     if (s->stream) (void)hipStreamDestroy(s->stream);

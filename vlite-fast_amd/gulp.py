@@ -4,8 +4,8 @@ import sys
 
 import numpy as np
 
-from .candidates import (candidates_from_giants, candidates_from_peaks, candidates_from_subbands, parse_coincidencer,
-                         send_candidates)
+from .candidates import (candidates_from_giants, candidates_from_peaks, candidates_from_periodic, candidates_from_subbands,
+                         parse_coincidencer, send_candidates)
 from .searcher import CUTOUT_KEYS, POL_KEYS, block_arg
 
 
@@ -72,11 +72,22 @@ class GulpSearch(object):
     return the full-band candidates as before, followed by the sub-band candidates -- the ones that carry `band` -- of the
     same samples.  Cutouts, refinement and the coincidencer see the full-band candidates only; with send=True the sub-band
     candidates go to the coincidencer as well, as ordinary lines.  A gulp whose points exceed the searcher's max_points
-    yields no sub-band candidates and one log line."""
+    yields no sub-band candidates and one log line.
+    periodic=dict(thresh=8.0, max_per_gulp=64, p_range=None) (the searcher's set_periodic() must be on): every search is
+    followed by the periodicity search of the same block's series (Searcher.periodic, candidates_from_periodic) and push(),
+    feed() and flush() return its candidates -- the ones that carry `period_s` -- after all the others.  They describe the
+    whole block, the samples it shares with the block before it included, and never go to the coincidencer, whose wire
+    format has no period."""
 
     def __init__(self, searcher, threshold=6.0, nbit=8, coincidencer=None, utc_start="1970-01-01-00:00:00", beam=1,
-                 cutouts=None, refine=None, giants=None, gulp=None, pol=None, subbands=None):
+                 cutouts=None, refine=None, giants=None, gulp=None, pol=None, subbands=None, periodic=None):
         self.s, self.threshold, self.nbit = searcher, threshold, nbit
+        self.per = None
+        self.per_cands = []              # the periodicity candidates of the latest search, until _out() hands them on
+        if periodic is not None:
+            if searcher._per is None:
+                raise ValueError("GulpSearch(periodic=...): call the searcher's set_periodic() first")
+            self.per = (float(periodic.get("thresh", 8.0)), int(periodic.get("max_per_gulp", 64)), periodic.get("p_range"))
         self.sub = None
         if subbands is not None:
             if searcher._sub is None:
@@ -191,9 +202,11 @@ class GulpSearch(object):
         return self._sub_cands(res, res["t"] < nout, sample0) if res is not None else []
 
     def _out(self, cands, sub, first, nsamps):
-        """send a batch (the sub-band candidates only with send=True) and return it, the sub-band candidates last"""
+        """send a batch (the sub-band candidates only with send=True, the periodicity candidates never) and return it, the
+        sub-band candidates after the full-band ones, the periodicity candidates last"""
         self._send(cands + sub if (sub and self.sub[1]) else cands, first, nsamps)
-        return cands + sub
+        per, self.per_cands = self.per_cands, []
+        return cands + sub + per
 
     @staticmethod
     def _subset(pk, sel):
@@ -232,6 +245,9 @@ class GulpSearch(object):
         first = self.last_first = self.done
         if self.s._rfichan is not None:
             self.chan_log.append((first, self.s.rfi_chan_info()))
+        if self.per:
+            self.per_cands = candidates_from_periodic(self.s.periodic(), self.s.dms, self.s.tsamp, self.per[0], self.per[1],
+                                                      p_range=self.per[2])
         self._attach(cands, first)
         sub = self._sub_search(nout, pk["tout"], first) if self.sub else []
         self.done += nout

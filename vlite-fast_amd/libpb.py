@@ -61,7 +61,8 @@ EXPORTS = ["pb_config_default", "pb_create", "pb_destroy", "pb_last_error", "pb_
            "pb_search_set_planes", "pb_search_giant_timers", "pb_search_set_gulp", "pb_search_push", "pb_search_push_f32", "pb_search_gulp_peaks",
            "pb_search_gulp_run", "pb_search_gulp_advance", "pb_search_gulp_fetch", "pb_search_gulp_timers", "pb_search_set_pol",
            "pb_search_pol", "pb_search_pol_cutouts", "pb_search_pol_fetch", "pb_search_pol_timers", "pb_search_set_subbands",
-           "pb_search_subbands", "pb_search_subband_dm", "pb_search_subband_timers", "pb_search_set_rfi_chan",
+           "pb_search_subbands", "pb_search_subband_dm", "pb_search_subband_timers", "pb_search_set_periodic", "pb_search_periodic",
+           "pb_search_periodic_fold", "pb_search_periodic_timers", "pb_search_set_rfi_chan",
            "pb_search_rfi_chan_info", "pb_correlate_info", "pb_correlate", "pb_correlate_gated", "pb_correlate_timers",
            "pb_imager_create", "pb_imager_destroy", "pb_imager_last_error", "pb_imager_set_vis", "pb_imager_run",
            "pb_imager_timers", "pb_beamform", "pb_beamform_timers", "pb_beamform_proj", "pb_beamform_proj_timers",
@@ -186,6 +187,10 @@ def load():
     L.pb_search_subbands.argtypes = [vp, C.c_float, C.c_int, C.c_int, i32p, C.c_int, ip, ip]
     L.pb_search_subband_dm.argtypes = [vp, C.c_int, u32p, fp, u8p, fp, fp, u8p, u8p]
     L.pb_search_subband_timers.argtypes = [vp, fp]
+    L.pb_search_set_periodic.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.pb_search_periodic.argtypes = [vp, i32p]
+    L.pb_search_periodic_fold.argtypes = [vp, C.c_int, C.c_int, C.c_int, u32p, fp, i32p, ip, ip]
+    L.pb_search_periodic_timers.argtypes = [vp, fp]
     L.pb_search_set_rfi_chan.argtypes = [vp, C.c_int, C.c_float]
     L.pb_search_rfi_chan_info.argtypes = [vp, ip, u8p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), i32p, i32p, u8p, fp]
     L.pb_correlate_info.argtypes = [vp, ip, ip]

@@ -17,8 +17,9 @@ import argparse
 import numpy as np
 
 from . import sigproc as sig
-from .candidates import (candidate_line, candidates_from_giants, candidates_from_peaks, candidates_from_subbands,
-                         find_candidates, group_points, overlap, subband_list)
+from .candidates import (PERIODIC_BINS, candidate_line, candidates_from_giants, candidates_from_peaks,
+                         candidates_from_periodic, candidates_from_subbands, find_candidates, group_points, harmonic_ratio,
+                         overlap, periodic_octaves, subband_list)
 from .gulp import GulpSearch, gulp_cuts
 from .searcher import (CUTOUT_KEYS, FCH1, FOFF, HEIMDALL_BOXCAR_MAX, HEIMDALL_DM, HEIMDALL_GULP, HEIMDALL_ZAP,
                        POL_KEYS, TSAMP, Searcher, dedisp_dm_list)
@@ -32,7 +33,9 @@ def arg_parser(with_file=True):
                                         "a nifs 4 filterbank (AA, BB, CR, CI); Stokes spectra and RM synthesis of the strongest "
                                         "candidates (pol_parser).  Also: -subbands N [-subband_thresh S] [-subband_send]: search N base "
                                         "sub-bands (2, 4, 8 or 16) and their staggered dyadic runs for band-limited bursts "
-                                        "(subband_parser)")
+                                        "(subband_parser).  Also: -periodic P_LO P_HI [-periodic_bins B] [-periodic_thresh S] "
+                                        "[-periodic_max N]: fold every trial DM's series at the periods P_LO .. P_HI seconds "
+                                        "(periodic_parser)")
     if with_file:
         ap.add_argument("-f", dest="fil", required=True)
     ap.add_argument("-dm", nargs=2, type=float, default=list(HEIMDALL_DM))
@@ -89,6 +92,17 @@ def subband_parser():
     return ap
 
 
+def periodic_parser():
+    """the flags of -periodic, parsed apart from arg_parser()'s like -pol's: a command line without them gives the namespace
+    it always gave"""
+    ap = argparse.ArgumentParser(prog="search", prefix_chars="-", add_help=False, allow_abbrev=False)
+    ap.add_argument("-periodic", nargs=2, type=float, default=None, metavar=("P_LO", "P_HI"), help="search every trial DM's series for periodic pulses with periods P_LO .. P_HI seconds by folding (FFA); with -output_dir a .periodic file beside each .cand")
+    ap.add_argument("-periodic_bins", type=int, default=None, help="with -periodic: profiles of B .. 2B - 1 bins, B 32, 64 or 128 (default 64)")
+    ap.add_argument("-periodic_thresh", type=float, default=None, help="with -periodic: lowest folded S/N reported (default 8.0)")
+    ap.add_argument("-periodic_max", type=int, default=None, help="with -periodic: most periodicity candidates per gulp (default 64)")
+    return ap
+
+
 def rfichan_parser():
     """the flags of -rfi_chan, parsed apart from arg_parser()'s like -pol's: a command line without them gives the namespace
     it always gave"""
@@ -101,8 +115,8 @@ def rfichan_parser():
 
 def parse_flags(flags):
     """process_baseband's --search "<flags>": the string split as a shell would and parsed by the search's own parser
-    (arg_parser(with_file=False) and parse_args' checks); an unknown flag, -f, -stream_chunk or -pol ends in SystemExit; -subbands
-    and -rfi_chan and their flags are taken"""
+    (arg_parser(with_file=False) and parse_args' checks); an unknown flag, -f, -stream_chunk or -pol ends in SystemExit; -subbands,
+    -periodic and -rfi_chan and their flags are taken"""
     import shlex
     return parse_args(shlex.split(flags), with_file=False)
 
@@ -128,6 +142,24 @@ def _subband_checks(ap, a, sa, argv, with_file):
         sa.subband_thresh = a.detect_thresh
 
 
+def _periodic_checks(ap, a, pa, argv, with_file):
+    alone = [f for f in ("-periodic_bins", "-periodic_thresh", "-periodic_max") if getattr(pa, f[1:]) is not None]
+    if alone and pa.periodic is None:
+        ap.error("%s: only with -periodic" % ", ".join(alone))
+    if pa.periodic is not None:
+        if "-pol" in argv:
+            ap.error("-periodic is not combined with -pol")
+        for k, v in (("periodic_bins", 64), ("periodic_thresh", 8.0), ("periodic_max", 64)):
+            if getattr(pa, k) is None:
+                setattr(pa, k, v)
+        if pa.periodic_bins not in PERIODIC_BINS:
+            ap.error("-periodic_bins must be 32, 64 or 128")
+        if not (0 < pa.periodic[0] <= pa.periodic[1]) or not np.isfinite(pa.periodic[1]):
+            ap.error("-periodic P_LO P_HI: need 0 < P_LO <= P_HI, in seconds")
+        if pa.periodic_thresh != pa.periodic_thresh or pa.periodic_max < 1:
+            ap.error("-periodic_thresh must be a number, -periodic_max >= 1")
+
+
 def _pol_checks(ap, a, pa, argv, with_file):
     alone = [f for f in ("-pol_thresh", "-pol_max", "-rm", "-rm_step", "-pol_off") if f in argv]
     if alone and not pa.pol:
@@ -151,7 +183,7 @@ def _pol_checks(ap, a, pa, argv, with_file):
 
 # the flags parsed apart from arg_parser()'s: (their parser, the flag that switches them on, the checks between them)
 _SIDE_FLAGS = ((rfichan_parser, "rfi_chan", _rfichan_checks), (subband_parser, "subbands", _subband_checks),
-              (pol_parser, "pol", _pol_checks))
+              (periodic_parser, "periodic", _periodic_checks), (pol_parser, "pol", _pol_checks))
 
 
 def parse_args(argv=None, with_file=True):
@@ -287,6 +319,18 @@ def write_subbands(path, cands):
     return _write_lines(path, [c for c in cands if "band" in c], subband_line)
 
 
+def periodic_line(c):
+    """a periodicity candidate's line: snr period_s dm width_s phase dmi k p i m nharm"""
+    return "%.4f\t%.9f\t%.4f\t%.9f\t%.6f\t%d\t%d\t%d\t%d\t%d\t%s" % (c["snr"], c["period_s"], c["dm"], c["width_s"], c["phase"],
+                                                                        c["dmi"], c["k"], c["p"], c["i"], c["m"], c["nharm"])
+
+
+def write_periodic(path, cands):
+    """The periodicity candidates of one gulp (those that carry `period_s`), one periodic_line each.  Returns how many were
+    written (0: no file)."""
+    return _write_lines(path, [c for c in cands if "period_s" in c], periodic_line)
+
+
 def write_chans(path, info, s):
     """One gulp's channel mask (Searcher.rfi_chan_info): the line `# nflag nact radius tol`, then `channel S fill recv` for
     every flagged channel, ascending.  Written for every gulp searched with the channel stage on, flagged channels or not."""
@@ -353,10 +397,18 @@ def open_search(a, hdr, gulp, device=None, searcher=None):
             raise SystemExit("search -subbands: %d does not divide the %d channels" % (a.subbands, nchan))
         s.set_subbands(nsb=a.subbands)
         sub = dict(thresh=a.subband_thresh, send=a.subband_send)
+    per = None
+    if getattr(a, "periodic", None):
+        try:
+            k_lo, k_hi = periodic_octaves(a.periodic[0], a.periodic[1], a.periodic_bins, tsamp)
+            s.set_periodic(bins=a.periodic_bins, k_lo=k_lo, k_hi=k_hi)
+        except ValueError as e:
+            raise SystemExit("search -periodic: %s" % e)
+        per = dict(thresh=a.periodic_thresh, max_per_gulp=a.periodic_max, p_range=tuple(a.periodic))
     gi = dict(sep_time=a.cand_sep_time, sep_dm=a.cand_sep_dm, sep_filter=a.cand_sep_filter,
               max_giants=a.max_giants) if a.giants else None
     g = GulpSearch(s, threshold=a.detect_thresh, coincidencer=a.coincidencer, utc_start=utc, beam=a.beam, cutouts=cut,
-                   refine=ref, giants=gi, gulp=gulp, pol=pol, subbands=sub)
+                   refine=ref, giants=gi, gulp=gulp, pol=pol, subbands=sub, periodic=per)
     if a.output_dir:
         os.makedirs(a.output_dir, exist_ok=True)
     stems = set()
@@ -369,12 +421,15 @@ def open_search(a, hdr, gulp, device=None, searcher=None):
         return stem
 
     def emit(batch):
-        cands = [c for c in batch if "band" not in c]
+        cands = [c for c in batch if "band" not in c and "period_s" not in c]
         for c in cands:
             print(candidate_line(c))
         for c in batch:
             if "band" in c:
                 print(subband_line(c))
+        for c in batch:
+            if "period_s" in c:
+                print(periodic_line(c))
         stem = new_stem(g.last_first) if a.output_dir and batch else None
         if a.output_dir:                            # the channel masks of the gulps that the call searched
             for first, info in g.chan_log:                # (beside the batch's .cand where the gulp is the batch's)
@@ -386,6 +441,8 @@ def open_search(a, hdr, gulp, device=None, searcher=None):
                     f.write("".join(candidate_line(c) + "\n" for c in cands))
             if sub:
                 write_subbands(os.path.join(a.output_dir, stem + ".subband"), batch)
+            if per:
+                write_periodic(os.path.join(a.output_dir, stem + ".periodic"), batch)
             if a.cutouts:
                 write_cutouts_npz(os.path.join(a.output_dir, stem + ".cutouts.npz"), cands, tsamp)
             if a.refine:
@@ -415,6 +472,10 @@ def main(argv=None):
     pb_search_set_subbands; -subband_thresh, default -detect_thresh): the sub-band candidates are printed after the gulp's
     full-band lines, each as its nine columns followed by band_first band_count f_lo f_hi snr_full, and with -output_dir
     written to a .subband file beside .cand, which stays as it is; -subband_send also sends them to the coincidencer.
+    -periodic P_LO P_HI follows each gulp's search with the periodicity search of every trial DM's series (include/pb_hip.h,
+    pb_search_set_periodic; -periodic_bins, -periodic_thresh, -periodic_max): the candidates, grouped by harmonic ratio
+    (candidates_from_periodic), are printed last as snr period_s dm width_s phase dmi k p i m nharm and with -output_dir
+    written to a .periodic file beside .cand; nothing periodic goes to the coincidencer.
     -stream_chunk M reads the file in pieces of M samples and feeds them to GulpSearch(gulp=-nsamps_gulp): the same
     lines, gathered on the GPU as a host behind pb_process would gather them; on this path 4- and 2-bit files are
     accepted and fed packed."""

@@ -49,9 +49,11 @@ Gi = namedtuple("Gi", "sep_time sep_dm sep_filter max_giants")
 Pol = namedtuple("Pol", "off_len guard rm max_cands")             # rm = (rm_lo, rm_step, nrm)
 Sub = namedtuple("Sub", "nsb bands max_points")                   # bands = [(first, count), ..]
 RfiChan = namedtuple("RfiChan", "radius tol")
+Per = namedtuple("Per", "bins k_lo k_hi")
 # attribute -> (the subject of "... not switched on", the call that switches it on)
 STAGES = dict(_cut=("cutouts are", "set_cutouts"), _pol=("polarisation is", "set_pol"), _ref=("refinement is", "set_refine"),
-              _sub=("the sub-band search is", "set_subbands"), _gi=("giants are", "set_giants"))
+              _sub=("the sub-band search is", "set_subbands"), _gi=("giants are", "set_giants"),
+              _per=("the periodicity search is", "set_periodic"))
 POL_KEYS = ("on", "non", "off", "noff", "F", "kbest", "summary")  # of Searcher.pol, one entry per request
 CUTOUT_KEYS = ("ft", "ft_hits", "dt", "dt_hits", "dm_rows")       # of Searcher.cutouts, one entry per request
 
@@ -120,9 +122,11 @@ class Searcher(object):
         self._pol = None                 # Pol(off_len, guard, (rm_lo, rm_step, nrm), max_cands) once set_pol has switched it on
         self._sub = None                 # Sub(nsb, [(first, count), ..], max_points) once set_subbands has switched it on
         self._rfichan = None             # RfiChan(radius, tol) once set_rfi_chan has switched the channel stage on
+        self._per = None                 # Per(bins, k_lo, k_hi) once set_periodic has switched it on
         self.dms = dm_min + dm_step * np.arange(self.ndm) if dm_list is None else np.asarray(dm_list, np.float64)
         self._nsamp = 0
-        self._tout = 0
+        self._tout = 0                   # output samples of the planes on the device (the last search's, or set_planes')
+        self._tsearch = 0                # output samples of the last search: the length of its series
 
     def _check(self, rc, name, exc=None, handle=True):
         """raise for a non-zero return code: PbError("<name> failed (rc): <last error>"), or exc(<last error>)"""
@@ -447,6 +451,58 @@ class Searcher(object):
         and best band; everything with the copy to the host"""
         return self._timers(self._L.pb_search_subband_timers, ("dedisperse", "stats", "boxcar", "with_copy"))
 
+    def set_periodic(self, bins=64, k_lo=0, k_hi=0, dm_chunk=0):
+        """the periodicity search (include/pb_hip.h, pb_search_set_periodic): profiles of bins .. 2 bins - 1 bins (bins 32, 64
+        or 128) at the octaves k_lo .. k_hi (series summed in 2^k samples), the trial DMs processed dm_chunk at a time (0: what
+        keeps the stage's scratch within 1 GiB); bins=0 switches the stage off"""
+        rc = self._L.pb_search_set_periodic(self._s, int(bins), int(k_lo), int(k_hi), int(dm_chunk))
+        self._check(rc, None, ValueError)
+        self._per = Per(int(bins), int(k_lo), int(k_hi)) if bins else None
+
+    def periodic_rows(self, k, p):
+        """(m, M) of base period p at octave k for the last block searched: rows folded, and trials (0: skipped)"""
+        m = (self._tsearch >> int(k)) // int(p)
+        return m, (1 << int(m - 1).bit_length()) if m >= 2 else 0
+
+    def periodic(self):
+        """pb_search_periodic on the series of the last run() / peaks() / gulp search: the best trial of every trial DM,
+        octave and base period.  Returns dict(snr f32, i, q, j i32, m, M i32, period_s f64 -- all [ndm][nk][bins], the entry
+        of base period p at p - bins; octaves [nk], p [bins]).  A skipped base period has snr 0, i -1 and period_s NaN;
+        m, M and period_s = (p + i / (M - 1)) 2^k tsamp are made on the host."""
+        B, k_lo, k_hi = self._stage("_per")
+        nk = k_hi - k_lo + 1
+        buf = np.empty((self.ndm, nk, B, 4), np.int32)
+        rc = self._L.pb_search_periodic(self._s, buf.ctypes.data_as(C.POINTER(C.c_int32)))
+        self._check(rc, "pb_search_periodic")
+        ks, ps = np.arange(k_lo, k_hi + 1), np.arange(B, 2 * B)
+        mM = np.array([[self.periodic_rows(k, p) for p in ps] for k in ks], np.int32)
+        m, M = [np.broadcast_to(mM[None, :, :, c], buf.shape[:3]).copy() for c in (0, 1)]
+        i = buf[..., 1].copy()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            per = (ps[None, None, :] + i / (M - 1.0)) * (2.0 ** ks)[None, :, None] * self.tsamp
+        return dict(snr=buf[..., 0].copy().view(np.float32), i=i, q=buf[..., 2].copy(), j=buf[..., 3].copy(), m=m, M=M,
+                    period_s=np.where(i >= 0, per, np.nan), octaves=ks, p=ps)
+
+    def periodic_fold(self, dmi, k, p):
+        """one (trial DM, octave, base period) in full (tests; the profile of a candidate): dict(m, M, prof [M][p] u32, snr
+        [M][Q + 1] f32, jbest [M][Q + 1] i32, widths [Q + 1]); a skipped base period gives M = 0 and empty arrays"""
+        B = self._stage("_per").bins
+        nq = int(B // 2).bit_length()
+        m, Mo = C.c_int(), C.c_int()
+        rc = self._L.pb_search_periodic_fold(self._s, int(dmi), int(k), int(p), None, None, None, C.byref(m), C.byref(Mo))
+        self._check(rc, "pb_search_periodic_fold")             # (no output asked for: the sizes only, nothing launched)
+        M = Mo.value
+        out = dict(prof=np.zeros((M, int(p)), np.uint32), snr=np.zeros((M, nq), np.float32), jbest=np.zeros((M, nq), np.int32))
+        rc = self._L.pb_search_periodic_fold(self._s, int(dmi), int(k), int(p), out["prof"].ctypes.data_as(C.POINTER(C.c_uint32)),
+                                             out["snr"].ctypes.data_as(C.POINTER(C.c_float)),
+                                             out["jbest"].ctypes.data_as(C.POINTER(C.c_int32)), C.byref(m), C.byref(Mo))
+        self._check(rc, "pb_search_periodic_fold")
+        return dict(out, m=m.value, M=M, widths=1 << np.arange(nq))
+
+    def periodic_timers(self):
+        """device ms of the last periodic() call: the folding; the last stage and the evaluation; everything with the copy"""
+        return self._timers(self._L.pb_search_periodic_timers, ("fold", "eval", "with_copy"))
+
     def set_giants(self, sep_time=3, sep_dm=200, sep_filter=3, max_giants=1 << 18):
         """giants and clusters of giants on the device (include/pb_hip.h, pb_search_set_giants): hot samples of a series
         at most sep_time apart make a giant, giants within sep_dm trial DMs, sep_filter in log2 width and sep_time in time
@@ -517,7 +573,7 @@ class Searcher(object):
                                      buf.ctypes.data_as(C.POINTER(C.c_int32)), max_out, C.byref(n), C.byref(t))
         self._check(rc, "pb_search_peaks")
         self._nsamp = nsamp
-        self._tout = t.value
+        self._tout = self._tsearch = t.value
         return peak_dict(buf, n.value, t.value, max_out)
 
     def set_gulp(self, keep_max):
@@ -557,7 +613,7 @@ class Searcher(object):
                                           C.byref(n), C.byref(t))
         self._check(rc, "pb_search_gulp_peaks")
         self._nsamp = t.value + self.max_delay
-        self._tout = t.value
+        self._tout = self._tsearch = t.value
         return peak_dict(buf, n.value, t.value, max_out)
 
     def gulp_run(self, want_series=False):
@@ -568,7 +624,7 @@ class Searcher(object):
         rc = self._L.pb_search_gulp_run(self._s, *ptrs, C.byref(t))
         self._check(rc, "pb_search_gulp_run")
         self._nsamp = fill
-        self._tout = t.value
+        self._tout = self._tsearch = t.value
         return dict(out, tout=t.value)
 
     def gulp_fill(self):
@@ -611,6 +667,6 @@ class Searcher(object):
         rc = self._L.pb_search_run(self._s, ptr, on_dev, nsamp, nbit, *ptrs, C.byref(t))
         self._check(rc, "pb_search_run")
         self._nsamp = nsamp
-        self._tout = tout
+        self._tout = self._tsearch = tout
         return dict(out, tout=tout)
 
