@@ -72,6 +72,20 @@ if hasattr(L, "pb_internal_d2_wg") or True:
         a = np.frombuffer(buf, dtype=np.uint64).reshape(64, 256, 4).astype(np.int64)
         n = a[:, 0, 3]
         order = np.argsort(n)
+        # where and when the two workgroups of a channel group ran.  D2_PAIR_APART: blocks between partners -- 128 with
+        # d2_block_map.h (the excised one first) and for a library from before it (grid (128, 2): the raw one first),
+        # 8 for the paired order of profiles/r09_notes.md section 2
+        apart = int(os.environ.get("D2_PAIR_APART", "128"))
+        first = np.array([b for b in range(256) if (b % (2 * apart)) < apart])
+        for i in order[-8:-2]:
+            xcc = a[i, :, 2] & 0xff
+            d0 = (a[i, first + apart, 0] - a[i, first, 0]) / 100.0      # us, second of the pair minus first
+            d1 = (a[i, first + apart, 1] - a[i, first, 1]) / 100.0
+            print("launch %3d: pairs %d apart on the same XCC %d of %d (workgroups per XCC %s) | second starts after first (us) "
+                  "median %.1f p10 %.1f p90 %.1f | ends after median %.1f p10 %.1f p90 %.1f"
+                  % (n[i], apart, int((xcc[first] == xcc[first + apart]).sum()), first.size,
+                     np.bincount(xcc, minlength=8).tolist(), np.median(d0), np.percentile(d0, 10), np.percentile(d0, 90),
+                     np.median(d1), np.percentile(d1, 10), np.percentile(d1, 90)))
         for i in order[-8:-2]:
             t0 = a[i, :, 0].min()
             st = (a[i, :, 0] - t0) / 100.0          # us

@@ -41,6 +41,9 @@
 // (profiles/r04_notes.md section 9) converted on the loader wave and doubled detect's time.  Rows of the excised plane
 // that are not written hold stale values of earlier batches; nothing reads them.
 //
+// Grid: 1-D, one block per (channel group, stream) in the order of d2_block_map.h, antennas on z (a placement choice,
+// nothing more: no result depends on where or when a block runs).
+//
 // Exactness notes (all selects reproduce the reference's branches bit for bit):
 //   (double)w >= 0.2  <=>  w >= 0.2f   (0.2f is the smallest float above 0.2);
 //   0.5*(w+w) == w exactly; adding +0.0f to a sum that started at +0.0f is the identity;
@@ -49,6 +52,7 @@
 // HBM traffic: the power planes (4 B per row x channel x pol x stream) once; outputs 1/64 of it.
 #include <cstdlib>
 
+#include "d2_block_map.h"
 #include "pb_internal.h"
 #include "spectrum_div4.h"
 
@@ -310,8 +314,8 @@ template <int DEPTH> struct Cursor {
 }  // namespace
 
 template <int T, bool KUR, int NPOL, int NBIT, int DEPTH, int CONV>
-__device__ __forceinline__ void detect2_body(const Detect2Args &a, float (*s_p)[T][64], float4 (*s_u)[T / 4][64],
-                                             float (*s_u0)[64], float (*s_w)[T], unsigned *s_f)
+__device__ __forceinline__ void detect2_body(const Detect2Args &a, const int cg, float (*s_p)[T][64],
+                                             float4 (*s_u)[T / 4][64], float (*s_u0)[64], float (*s_w)[T], unsigned *s_f)
 {
     static_assert(CONV == 0 || KUR, "only the excised stream takes rows from the other plane");
     static_assert(CONV != 2 || DEPTH >= 2, "a chunk lands one step before the recurrence reads it");
@@ -319,7 +323,6 @@ __device__ __forceinline__ void detect2_body(const Detect2Args &a, float (*s_p)[
     // (Two detect workgroups per CU -- two antennas per handle -- already have their recurrence waves on different
     //  SIMDs: swapping waves 0 <-> 2 in the odd antennas' workgroups made detect 12 % slower alone, r05_notes.md.)
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int cg = blockIdx.x;
     constexpr int stream = KUR ? 1 : 0;
     constexpr int NQ = T / 4, NG = T / PB_NSCRUNCH;
     const int ant = blockIdx.z;
@@ -666,7 +669,7 @@ __device__ __forceinline__ void detect2_body(const Detect2Args &a, float (*s_p)[
         for (int k = 0; k < nstep; ++k) step_barrier();
     }
 #ifdef D2_STAMP
-    if (blockIdx.x == 17 && blockIdx.y == 1 && blockIdx.z == 0 && lane == 0) {
+    if (cg == 17 && KUR && blockIdx.z == 0 && lane == 0) {
         // accumulated over launches (launches of one stream follow one another): the reader takes differences
         g_d2_stamp[wave & 7][0] += (unsigned long long)clk.work;
         g_d2_stamp[wave & 7][1] += (unsigned long long)clk.wait;
@@ -674,7 +677,7 @@ __device__ __forceinline__ void detect2_body(const Detect2Args &a, float (*s_p)[
         g_d2_stamp[wave & 7][3] += 1ull;
     }
     if (wave == 0 && lane == 0 && blockIdx.z == 0) {
-        const unsigned wg = blockIdx.x + gridDim.x * blockIdx.y;
+        const unsigned wg = blockIdx.x;          // dispatch order: d2_block_map
         if (wg < 256) {
             const unsigned n = g_d2_wgcnt[wg]++;
             g_d2_wg[n & 63][wg][0] = wg_t0;
@@ -687,7 +690,7 @@ __device__ __forceinline__ void detect2_body(const Detect2Args &a, float (*s_p)[
 #endif
 }
 
-// MODE = rfi_mode: 0 raw stream only, 1 excised only, 2 both (blockIdx.y picks the stream)
+// MODE = rfi_mode: 0 raw stream only, 1 excised only, 2 both (d2_block_map: which block takes which stream)
 template <int T, int NPOL, int NBIT, int MODE, int DEPTH, int CONV>
 __global__ __launch_bounds__(CONV == 2 ? D2_THREADS_CONV : D2_THREADS) void k_detect2(Detect2Args a)
 {
@@ -703,8 +706,13 @@ __global__ __launch_bounds__(CONV == 2 ? D2_THREADS_CONV : D2_THREADS) void k_de
     __shared__ float s_w[D2_NW][T];
     __shared__ unsigned s_f[8];
     // (the raw stream's workgroups of a CONV == 2 launch have two idle waves: one block size per launch)
-    if (MODE == 0 || (MODE == 2 && blockIdx.y == 0)) detect2_body<T, false, NPOL, NBIT, DEPTH, 0>(a, s_p, s_u, s_u0, s_w, s_f);
-    else detect2_body<T, true, NPOL, NBIT, DEPTH, CONV>(a, s_p, s_u, s_u0, s_w, s_f);
+    const d2_block blk = d2_block_map((int)blockIdx.x, MODE == 2 ? 2 : 1);
+#if defined(D2_ABL) && (D2_ABL & 2)
+    if (blk.stream) return;      // (timing experiment, RESULTS INVALID: only the raw stream's 128 workgroups -- what the step
+                                 //  would be with half of detect's workgroups at their present lifetime)
+#endif
+    if (MODE == 0 || (MODE == 2 && blk.stream == 0)) detect2_body<T, false, NPOL, NBIT, DEPTH, 0>(a, blk.cg, s_p, s_u, s_u0, s_w, s_f);
+    else detect2_body<T, true, NPOL, NBIT, DEPTH, CONV>(a, blk.cg, s_p, s_u, s_u0, s_w, s_f);
 }
 
 // conv: CONV of the excised stream (mode 2 only)
@@ -753,11 +761,8 @@ hipError_t launch_detect_pow(pb_handle *h, int nseg)
     a.scale = (float)(tsamp / 1.0);
     a.oms = 1 - a.scale;
     a.tscale = (float)sqrt(1. / PB_NSCRUNCH);
-    dim3 grid(PB_NCHANOUT / 32, h->cfg.rfi_mode == 2 ? 2 : 1, h->A);
-#if defined(D2_ABL) && (D2_ABL & 2)
-    grid.y = 1;      // (timing experiment, RESULTS INVALID: only the raw stream's 128 workgroups -- what the step would be
-                     //  with half of detect's workgroups at their present lifetime, the bound of a two-stream workgroup)
-#endif
+    // one block per (channel group, stream) in the order of d2_block_map, antennas on z
+    dim3 grid(PB_NCHANOUT / 32 * (h->cfg.rfi_mode == 2 ? 2 : 1), 1, h->A);
     // three chunks in flight where detect runs wholly beside the next batch's channeliser (it flags its own rows and
     // starts straight behind the previous one), two otherwise (measured both ways, see the comment on DEPTH)
     const int depth_env = h->sched.detect_depth;     // PB_DETECT_DEPTH 2 / 3: timing experiments
