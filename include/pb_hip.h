@@ -310,6 +310,46 @@ int pb_correlate_gated(pb_handle *h, int stream, int nseg, const int32_t *row0, 
                        float *vis, int32_t *rows_used);
 int pb_correlate_timers(const pb_handle *h, float *ms2);
 
+/* ---- correlator with fringe stopping: pb_correlate_gated on spectra that each antenna's model has turned first.  A
+ * geometric delay changes while a batch lasts (on a 36 km baseline by about a sample, and three turns of phase, per
+ * second), so gates of more than a few tens of milliseconds lose the longer baselines unless every antenna's spectrum
+ * is turned by a phase that follows the row BEFORE the products are added over the rows.
+ * Definition (THIS project's own; tests/correlate_track_ref.py restates it): pb_correlate_tracked is pb_correlate_gated
+ * with every X[a][p][t][c] replaced by X'[a][p][t][c] before the term lines.
+ *   model      host binary64 [nant][4] = delay0, delay_rate, psi0, psi_rate: samples LATE at 128 MS/s, samples per row,
+ *              turns, turns per row.  row_base (int64): the batch's row 0 counted from the model's epoch, so that one
+ *              model continues over successive batches (batch k of T rows: row_base = k T).
+ *   per (a, t) on the host in binary64, t = 0 .. T - 1, every operation rounded once, none contracted:
+ *                  tau = (double)(row_base + t)
+ *                  d   = delay0 + delay_rate * tau          p = psi0 + psi_rate * tau
+ *                  s   = d / 12500.0
+ *              The two tables s[a][t] and p[a][t] are what the device receives (at most 8 x 10240 doubles each).
+ *   per (a, t, c) with k = 2155 + c, in binary64 on the device (the imager's phase):
+ *                  turn = p + (double)k * s       (a multiply, then an add)        r = (float)(turn - rint(turn))
+ *              (cr, sr) = the imager's rotation polynomial of r (the lines and coefficients above), then the
+ *              beamformer's voltage lines with w = (cr, sr), every line one binary32 operation, no contraction; both
+ *              pols of an antenna share the rotation:
+ *                  x'r = xr*cr - xi*sr          x'i = xi*cr + xr*sr
+ *              i.e. x exp(+2 pi i r): an antenna that is d late is aligned by its true delay (pb_beamform's sign).
+ *              The model's drift within a row is ignored (about 3 10^-4 turn on 36 km).
+ *   term, gates, sum order, rows_used, outputs: word for word those of pb_correlate_gated, applied to X'.
+ *   pb_correlate_tracked         row0 int32 [ngate][4096] on the host, or NULL: uniform gates of nrows rows, row0[g][c] =
+ *                                g * nrows; nrows must then divide the batch's rows and ngate equal their quotient.
+ *   pb_correlate_tracked_timers  device time of the last call in ms: the uploads with the prefix kernel; the kernels;
+ *                                the copy to the host.
+ * Runs on the SELECTED set on a stream of its own behind that set's channeliser and detect and returns when its outputs
+ * have arrived, as pb_correlate_gated does; its device buffers (the visibilities, rows_used, the first rows, the tables
+ * and, on the excised stream, the row counts) are its own, grow on demand, count in pb_query's device_bytes and are freed
+ * in pb_destroy.  No other state of the handle changes: what pb_fetch and pb_correlate return afterwards is what they
+ * return without the call.
+ * Refused on the host before anything is queued, with a pb_last_error text: PB_EINVAL for everything pb_correlate_gated
+ * refuses (with row0 == NULL: nrows not dividing the batch or ngate not the quotient), a NULL model, a model entry that
+ * is not finite, |d| or |p| above 2^24 at either end of the batch (they are linear in the row, so the ends bound them),
+ * a row_base within the batch's rows of the largest int64; PB_ESTATE as for the gated call. */
+int pb_correlate_tracked(pb_handle *h, int stream, int nseg, const int32_t *row0, int ngate, int nrows,
+                         const double *model, int64_t row_base, float *vis, int32_t *rows_used);
+int pb_correlate_tracked_timers(const pb_handle *h, float *ms3);
+
 /* ---- imager: gated visibilities summed over delay hypotheses (reference: analysis/loc_step2.py :91-120, the scan of
  * each baseline's cross power over fractional delays, and analysis/loc_step3.py :287-348, every baseline's delay on a
  * sky grid).  Both are one operation: for each hypothesis (a "pixel": one delay and one phase per baseline) rotate each

@@ -11,9 +11,19 @@ coherence = 1 handle keeps); everything in this module is host-side numpy on its
 Command line (offline; the dump files are those the hosts' --replay reads):
 
   python -m vlite-fast_amd.correlate --replay ant0.uw ant1.uw ... [--offsets n0 n1 ...] [--stream raw|kur]
-         [--int-rows N] [--seconds N] [--dm DM --t0 ROW --width ROWS [--off-gates K]] -o out.npz
+         [--int-rows N] [--seconds N] [--dm DM --t0 ROW --width ROWS [--off-gates K]]
+         [--track --antennas ants.txt --centre RA_DEG DEC_DEG --time UNIX [--clock-ns c0 c1 ...] | --track-model m.txt]
+         -o out.npz
   (--rows-per-seg R --max-seg S: the handle's batch, 1024 x 10 rows = one second by default; a file's tail that does not
   fill a batch is left out, and the gates of --dm must lie within one batch)
+
+--track stops the fringes (pb_correlate_tracked): every antenna's spectra are turned, row by row, by a delay and a phase
+that drift linearly, before the products are added -- for anything integrated longer than a few tens of milliseconds on
+long baselines.  The model is localise.track_model's for the position --centre at --time, the time of the data's first
+row (ants.txt as for localise), taken relative to antenna 0; or --track-model reads it: one line of delay0 delay_rate
+psi0 psi_rate per antenna (samples late, samples per row, turns, turns per row).  Batch k is correlated with row_base =
+k * S * R, the ungated sum and the --dm gates alike; out.npz then also holds track_model [nant][4] and track_row_base
+[batches].  Without --track / --track-model nothing changes.
 
 out.npz: vis complex128 [nbl][4][4096] (all gates added in double), rows_used int64 [nbl][4096], baselines [nbl][2],
 freqs_mhz [4096], lag_cycles / lag_samples [2 pols][nant][nant] (pol products 0 and 3), fit_samples [2][nant] and
@@ -131,6 +141,12 @@ def make_parser():
     p.add_argument("--t0", type=int, default=None, help="row (from the start of the data) of the pulse in channel 0")
     p.add_argument("--width", type=int, default=None, help="rows per on / off gate")
     p.add_argument("--off-gates", type=int, default=2, help="off gates before and after the on gate")
+    p.add_argument("--track", action="store_true", help="stop the fringes with the geometric model of --centre at --time")
+    p.add_argument("--antennas", help="`name X Y Z` per antenna, metres, Earth-fixed")
+    p.add_argument("--centre", nargs=2, type=float, metavar=("RA_DEG", "DEC_DEG"))
+    p.add_argument("--time", type=float, help="unix time of the data's first row")
+    p.add_argument("--clock-ns", nargs="+", type=float, default=None, help="clock delay per antenna")
+    p.add_argument("--track-model", help="stop the fringes with this model: delay0 delay_rate psi0 psi_rate per antenna")
     return p
 
 
@@ -148,7 +164,54 @@ def parse_args(argv=None):
             p.error("--dm, --t0 and --width go together")
         if a.dm < 0 or a.t0 < 0 or a.width <= 0:
             p.error("--dm and --t0 must not be negative, --width must be positive")
+    geometry = (a.antennas, a.centre, a.time)
+    if a.track and a.track_model is not None:
+        p.error("--track builds the model from geometry and --track-model reads it: give one of them")
+    if a.track:
+        if any(v is None for v in geometry):
+            p.error("--track needs --antennas, --centre and --time")
+        if not -90.0 <= a.centre[1] <= 90.0:
+            p.error("--centre: the declination must lie within -90..90 degrees")
+    elif any(v is not None for v in geometry) or a.clock_ns is not None:
+        p.error("--antennas, --centre, --time and --clock-ns belong to --track")
     return a
+
+
+def read_track_model(path, nant):
+    """m.txt -> float64 [nant][4]; ValueError for a malformed line or a wrong count"""
+    rows = []
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            w = line.split("#")[0].split()
+            if not w:
+                continue
+            try:
+                rows.append([float(v) for v in w])
+            except ValueError:
+                rows.append(None)
+            if rows[-1] is None or len(w) != 4:
+                raise ValueError("%s:%d: expected `delay0 delay_rate psi0 psi_rate`" % (path, ln))
+    if len(rows) != nant:
+        raise ValueError("%s: %d antennas, --replay has %d" % (path, len(rows), nant))
+    return np.array(rows, np.float64)
+
+
+def tracking_model(args):
+    """the model of --track / --track-model, float64 [nant][4], or None"""
+    nant = len(args.replay)
+    try:
+        if args.track_model is not None:
+            return read_track_model(args.track_model, nant)
+        if args.track:
+            loc = importlib.import_module("vlite-fast_amd.localise")
+            _, xyz = loc.read_antennas(args.antennas, nant)
+            if args.clock_ns is not None and len(args.clock_ns) != nant:
+                raise ValueError("--clock-ns: one value per antenna (%d)" % nant)
+            m = loc.track_model(xyz, np.radians(args.centre[0]), np.radians(args.centre[1]), args.time, args.clock_ns)
+            return m - m[0]            # what all antennas share leaves every product; the delays stay within the array's
+    except (ValueError, IOError) as e:
+        raise SystemExit("correlate: %s" % e)
+    return None
 
 
 def run(args):
@@ -157,6 +220,7 @@ def run(args):
     vis = np.zeros((len(bls), 4, NCHANOUT), np.complex128)
     rows_used = np.zeros((len(bls), NCHANOUT), np.int64)
     gates = None
+    model, row_bases = tracking_model(args), []
     if args.dm is not None:
         K = args.off_gates
         starts = [args.t0 + (m - K) * args.width for m in range(2 * K + 1)]
@@ -167,11 +231,19 @@ def run(args):
             raise SystemExit("correlate: the gates must lie within one batch of %d rows (%s)" % (S * R, e))
         gates = dict(batch=batch, row0=row0)
     for k, h, stream in replay_batches.batches(args, "correlate"):
-        v, u = h.correlate(stream, S, args.int_rows)
+        if model is None:
+            v, u = h.correlate(stream, S, args.int_rows)
+        else:
+            row_bases.append(k * S * R)
+            v, u = h.correlate_tracked(stream, S, model, row_base=k * S * R, nrows=args.int_rows)
         vis += v.astype(np.complex128).sum(axis=0)
         rows_used += u.astype(np.int64).sum(axis=0)
         if gates is not None and gates["batch"] == k:
-            gates["vis"], gates["used"] = h.correlate_gated(stream, S, gates["row0"], args.width)
+            if model is None:
+                gates["vis"], gates["used"] = h.correlate_gated(stream, S, gates["row0"], args.width)
+            else:
+                gates["vis"], gates["used"] = h.correlate_tracked(stream, S, model, row_base=k * S * R, row0=gates["row0"],
+                                                                  nrows=args.width)
         nsec = k + 1                             # batches done
     if gates is not None and "vis" not in gates:
         raise SystemExit("correlate: --t0 lies beyond the %d batches read" % nsec)
@@ -182,6 +254,8 @@ def run(args):
                fit_samples=np.stack([f[0] for f in fits]), fit_model=np.stack([f[1] for f in fits]),
                delay_samples=-np.stack([f[0] for f in fits]),
                rows=np.int64(nsec * S * R), options=np.array(json.dumps(vars(args), sort_keys=True)))
+    if model is not None:
+        out.update(track_model=model, track_row_base=np.array(row_bases, np.int64))
     if gates is not None:
         out.update(gate_vis=gates["vis"], gate_rows_used=gates["used"],
                    gate_row0=gates["row0"].astype(np.int64) + gates["batch"] * S * R, gate_on=np.int64(args.off_gates))

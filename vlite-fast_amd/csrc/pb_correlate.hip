@@ -13,34 +13,17 @@
 //   (k_correlate<4, N, false>: 4 N baselines).
 // k_corr_prefix: per baseline the running count of rows whose weight is > 0 for both antennas (one wave, ballots), so
 //   that rows_used of the excised stream is a difference of two entries.
+// What the fringe-stopping kernel (pb_correlate_track.hip) shares with these -- the arguments, the loader's walk over a
+// window, one term, the stores, the prefix kernel's launch -- is correlate_dev.h.
 // Host side: pb_corr_state is a job of csrc/pb_job.h (stream, stage events and times, owned buffers that grow, teardown),
 // and what the calls refuse about the handle, the stream and the batch is that header's spectra_check_*.
-#include "pb_job.h"
-
-struct CorrArgs {
-    const float2 *X;       // one stream's spectra [A][S][2][R][4096]
-    const int32_t *row0;   // [ngate][4096] first row of the gate per channel
-    const int32_t *pref;   // [nbl][T + 1] rows before t with both weights > 0; nullptr on the raw stream
-    float2 *vis;           // [ngate][nbl][4][4096]
-    int32_t *used;         // [ngate][nbl][4096]
-    int A, S, R, T, nrows;
-    int i0, j0;            // first antenna of the tile's rows and columns
-};
+#include "correlate_dev.h"
 
 struct PB_LOCAL pb_corr_state : PbJob<2> {      // stages: kernels, copy to the host
     DevBuf<float> vis;
     DevBuf<int32_t> used, row0, pref;
     std::vector<int32_t> h_row0;
 };
-
-namespace {
-
-__host__ __device__ inline int corr_bl(int A, int i, int j) { return i * A - i * (i - 1) / 2 + (j - i); }
-
-// rows in flight per buffer: about 32 8-byte loads per lane and buffer
-constexpr int corr_rows_in_flight(int nl) { return nl == 1 ? 16 : nl == 2 ? 8 : nl == 3 ? 5 : nl == 4 ? 4 : 2; }
-
-}  // namespace
 
 template <int NI, int NJ, bool DIAG>
 __global__ __launch_bounds__(64) void k_correlate(CorrArgs a)
@@ -59,9 +42,7 @@ __global__ __launch_bounds__(64) void k_correlate(CorrArgs a)
         const int ant = (DIAG || l < NI) ? a.i0 + l : a.j0 + (l - NI);
         xp[l] = a.X + (size_t)ant * ant_stride + c;
     }
-    // the loader's position: row k of the window, as (row within its segment, offset of that row in an antenna's plane)
-    int kload = 0, row = r0 % R;
-    size_t off = (size_t)(r0 / R) * seg_stride + (size_t)row * PB_NCHANOUT;
+    CorrWalk w(r0, R, seg_stride);
 
     float2 cur[U][NL][2], nxt[U][NL][2];
     auto request = [&]() {
@@ -69,19 +50,10 @@ __global__ __launch_bounds__(64) void k_correlate(CorrArgs a)
         for (int u = 0; u < U; ++u) {
 #pragma unroll
             for (int l = 0; l < NL; ++l) {
-                nxt[u][l][0] = xp[l][off];
-                nxt[u][l][1] = xp[l][off + pol_stride];
+                nxt[u][l][0] = xp[l][w.off];
+                nxt[u][l][1] = xp[l][w.off + pol_stride];
             }
-            // rows past the window's end repeat its last row (loaded, never added): no address leaves the window
-            if (kload < nrows - 1) {
-                ++kload;
-                ++row;
-                off += PB_NCHANOUT;
-                if (row == R) {
-                    row = 0;
-                    off += seg_stride - pol_stride;
-                }
-            }
+            w.step(nrows, R, seg_stride, pol_stride);
         }
     };
 
@@ -113,43 +85,19 @@ __global__ __launch_bounds__(64) void k_correlate(CorrArgs a)
 #pragma unroll
                         for (int p = 0; p < 2; ++p)
 #pragma unroll
-                            for (int q = 0; q < 2; ++q) {
-                                // one term (include/pb_hip.h): the lines of the coherence definition
-                                const float ax = cur[u][i][p].x, ay = cur[u][i][p].y;
-                                const float bx = cur[u][lj][q].x, by = cur[u][lj][q].y;
-                                const float rxx = ax * bx, ryy = ay * by;
-                                const float re = rxx + ryy;
-                                const float iyx = ay * bx, ixy = ax * by;
-                                const float im = iyx - ixy;
-                                acc[b][2 * p + q].x = acc[b][2 * p + q].x + re;
-                                acc[b][2 * p + q].y = acc[b][2 * p + q].y + im;
-                            }
+                            for (int q = 0; q < 2; ++q) corr_term(acc[b][2 * p + q], cur[u][i][p], cur[u][lj][q]);
                         ++b;
                     }
             }
         }
     }
 
-    const int nbl = a.A * (a.A + 1) / 2;
     int b = 0;
 #pragma unroll
     for (int i = 0; i < NI; ++i)
 #pragma unroll
         for (int j = DIAG ? i : 0; j < (DIAG ? NI : NJ); ++j) {
-            const int bl = corr_bl(a.A, a.i0 + i, DIAG ? a.i0 + j : a.j0 + j);
-            const size_t o = (size_t)g * nbl + bl;
-            if (a.vis) {
-#pragma unroll
-                for (int pr = 0; pr < 4; ++pr) a.vis[(o * 4 + pr) * PB_NCHANOUT + c] = acc[b][pr];
-            }
-            if (a.used) {
-                int n = nrows;
-                if (a.pref) {
-                    const int32_t *P = a.pref + (size_t)bl * (a.T + 1);
-                    n = P[r0 + nrows] - P[r0];
-                }
-                a.used[o * PB_NCHANOUT + c] = n;
-            }
+            corr_store(a, g, c, r0, corr_bl(a.A, a.i0 + i, DIAG ? a.i0 + j : a.j0 + j), acc[b]);
             ++b;
         }
 }
@@ -171,6 +119,11 @@ __global__ __launch_bounds__(64) void k_corr_prefix(const float *wrow, int A, si
         if (t < T) P[t + 1] = total + __popcll(m & (~0ull >> (63 - lane)));
         total += __popcll(m);
     }
+}
+
+void corr_prefix_launch(const float *wrow, int A, size_t ant_stride, int T, int32_t *pref, hipStream_t st)
+{
+    k_corr_prefix<<<dim3(A, A), 64, 0, st>>>(wrow, A, ant_stride, T, pref);
 }
 
 template <int NI, int NJ, bool DIAG> static void corr_launch(const CorrArgs &a, int ngate, hipStream_t st)
@@ -232,7 +185,7 @@ static int corr_run(pb_handle *h, int stream, int nseg, int ngate, int nrows, fl
     a.nrows = nrows;
     a.i0 = a.j0 = 0;
     if (kur && rows_used) {
-        k_corr_prefix<<<dim3(h->A, h->A), 64, 0, cs->st>>>(b.d_wrow.p, h->A, (size_t)h->S * h->R, T, cs->pref.p);
+        corr_prefix_launch(b.d_wrow.p, h->A, (size_t)h->S * h->R, T, cs->pref.p, cs->st);
         a.pref = cs->pref.p;
     }
     corr_launch_all(a, ngate, cs->st);

@@ -264,6 +264,7 @@ extern "C" void pb_destroy(pb_handle *h)
     for (hipStream_t s : {h->stream, h->s_det.s, h->s_copy.s, h->s_kur.s})
         if (s) (void)hipStreamSynchronize(s);
     pb_correlate_free(h);
+    pb_correlate_track_free(h);
     pb_beamform_free(h);
     pb_beam_plane_free(h);
     for (auto &kv : h->plans) hipfftDestroy(kv.second);

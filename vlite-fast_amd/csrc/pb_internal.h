@@ -130,6 +130,7 @@ struct PB_LOCAL pb_handle {
     Event ev_coadd[2];
     int coadd_slot = 0, coadd_last = 0;
     struct pb_corr_state *corr = nullptr;   // the correlator's job (pb_job.h; pb_correlate.hip), from its first call on
+    struct pb_track_state *track = nullptr; // pb_correlate_tracked's (pb_correlate_track.hip), likewise
     struct pb_beam_state *beam = nullptr, *beamproj = nullptr;   // pb_beamform's and pb_beamform_proj's (pb_beamform.hip), likewise
     struct pb_plane_state *plane = nullptr;                      // pb_beam_planes' own buffers (pb_beam_plane.hip), likewise
     FftTables ft;
@@ -171,6 +172,7 @@ PB_LOCAL hipError_t sync_all(pb_handle *h);                          // pb_handl
 PB_LOCAL int pb_skip_mask();                                         // pb_handle.hip: PB_SKIP of the experiments build, else 0
 PB_LOCAL int pb_lean_lds(int dflt);                                  // pb_handle.hip, FFT_LEAN variant builds only
 PB_LOCAL void pb_correlate_free(pb_handle *h);                       // pb_correlate.hip: what pb_destroy releases
+PB_LOCAL void pb_correlate_track_free(pb_handle *h);                 // pb_correlate_track.hip: likewise
 PB_LOCAL void pb_beamform_free(pb_handle *h);                        // pb_beamform.hip: likewise, both calls' states
 PB_LOCAL void pb_beam_plane_free(pb_handle *h);                      // pb_beam_plane.hip: likewise
 // pb_tables.hip: what pb_create builds (twiddles and FIR taps; taps = 4: history slots and window energies; D'Agostino constants)

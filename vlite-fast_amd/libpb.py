@@ -64,6 +64,7 @@ EXPORTS = ["pb_config_default", "pb_create", "pb_destroy", "pb_last_error", "pb_
            "pb_search_subbands", "pb_search_subband_dm", "pb_search_subband_timers", "pb_search_set_periodic", "pb_search_periodic",
            "pb_search_periodic_fold", "pb_search_periodic_timers", "pb_search_set_rfi_chan",
            "pb_search_rfi_chan_info", "pb_correlate_info", "pb_correlate", "pb_correlate_gated", "pb_correlate_timers",
+           "pb_correlate_tracked", "pb_correlate_tracked_timers",
            "pb_imager_create", "pb_imager_destroy", "pb_imager_last_error", "pb_imager_set_vis", "pb_imager_run",
            "pb_imager_timers", "pb_beamform", "pb_beamform_timers", "pb_beamform_proj", "pb_beamform_proj_timers",
            "pb_beam_planes", "pb_beam_planes_timers"]
@@ -197,6 +198,8 @@ def load():
     L.pb_correlate.argtypes = [vp, C.c_int, C.c_int, C.c_int, fp, i32p, ip]
     L.pb_correlate_gated.argtypes = [vp, C.c_int, C.c_int, i32p, C.c_int, C.c_int, fp, i32p]
     L.pb_correlate_timers.argtypes = [vp, fp]
+    L.pb_correlate_tracked.argtypes = [vp, C.c_int, C.c_int, i32p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int64, fp, i32p]
+    L.pb_correlate_tracked_timers.argtypes = [vp, fp]
     L.pb_imager_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     L.pb_imager_destroy.argtypes = [vp]
     L.pb_imager_destroy.restype = None
@@ -464,6 +467,41 @@ class PbHandle(object):
         ms = np.zeros(2, np.float32)
         self._chk(self._L.pb_correlate_timers(self._h, _f32(ms)))
         return float(ms[0]), float(ms[1])
+
+    def correlate_tracked(self, stream, nseg, model, row_base=0, row0=None, nrows=None):
+        """correlate_gated() with fringe stopping (include/pb_hip.h: pb_correlate_tracked).  model: float64 [nant][4] =
+        delay0 (samples late), delay_rate (samples per row), psi0 (turns), psi_rate (turns per row); row_base: the
+        batch's row 0 counted from the model's epoch.  row0: int32 [ngate][4096] with nrows rows per gate, or None:
+        uniform gates of nrows rows (by default the whole batch).  -> (vis, rows_used) as correlate()"""
+        model = np.ascontiguousarray(model, np.float64)
+        if model.shape != (self.nant, 4):
+            raise ValueError("model must be [%d][4]" % self.nant)
+        if row0 is not None:
+            row0 = np.ascontiguousarray(row0, np.int32)
+            if row0.ndim != 2 or row0.shape[1] != NCHANOUT:
+                raise ValueError("row0 must be [ngate][%d]" % NCHANOUT)
+            if nrows is None:
+                raise ValueError("row0 needs nrows")
+            ngate = row0.shape[0]
+        else:
+            if nrows is None:
+                nrows = nseg * self.rows
+            ngate = max(1, nseg * self.rows // nrows) if nrows > 0 else 1
+        nbl, nprod = self.correlate_info()
+        vis = np.empty((ngate, nbl, nprod, NCHANOUT), np.complex64)
+        used = np.empty((ngate, nbl, NCHANOUT), np.int32)
+        self._chk(self._L.pb_correlate_tracked(self._h, stream, nseg,
+                                               row0.ctypes.data_as(C.POINTER(C.c_int32)) if row0 is not None else None,
+                                               ngate, nrows, model.ctypes.data_as(C.POINTER(C.c_double)), int(row_base),
+                                               vis.ctypes.data_as(C.POINTER(C.c_float)),
+                                               used.ctypes.data_as(C.POINTER(C.c_int32))))
+        return vis, used
+
+    def correlate_tracked_timers(self):
+        """device ms of the last correlate_tracked call: (uploads + row counts, kernels, copy to the host)"""
+        ms = np.zeros(3, np.float32)
+        self._chk(self._L.pb_correlate_tracked_timers(self._h, _f32(ms)))
+        return float(ms[0]), float(ms[1]), float(ms[2])
 
     # ---- beamformer (include/pb_hip.h: pb_beamform; needs coherence=True)
     def beamform(self, stream, nseg, delay, psi=None, gain=None, shift=None, tscr=1, nout=None):

@@ -8,6 +8,7 @@ channels, combine the baselines.  Everything in this module is host-side numpy o
   coarse_delays(u)                    whole-lag delays of weighted visibilities (the argmax of their lag spectrum)
   fine_delays(imager, coarse, ...)    the reference's fractional-delay scan and parabola (analysis/loc_step2.py:91-120)
   gmst_rad, precession_matrix, source_vector, antenna_delays, sky_grid     the geometry (see "Frame" below)
+  antenna_delay_rates, track_model    the delays' drift as the Earth turns; the fringe-stopping model of correlate --track
   antenna_to_baseline, phase_turns, baseline_phase                         per-antenna values to per-baseline ones
   tdoa_rms_map(measured, clock, tau_grid, mask)                            the rms map of analysis/loc_step3.py:312-348
 
@@ -212,6 +213,38 @@ def antenna_delays(xyz_m, s, clock_ns=None):
     if clock_ns is not None:
         d = d + np.asarray(clock_ns, float) * 1e-9 * VLITE_RATE
     return d
+
+
+EARTH_RATE = 2.0 * np.pi * 1.00273790935 / 86400.0      # rad / s: the rate of gmst_rad
+ROW_S = NFFT / VLITE_RATE                                # one FFT row, 97.65625 us
+
+
+def antenna_delay_rates(xyz_m, s, unix=None):
+    """the time derivative of antenna_delays(xyz_m, s) in samples per row of 12500 samples.  In the Earth-fixed frame
+    ds/dt = EARTH_RATE (s_y, -s_x, 0): the sidereal angle.  Precession moves s 10^-7 as fast (50" a year); with `unix`,
+    the time at which s = source_vector(.., unix) was taken, its term R3 dP/dt P^T R3^T s is added.
+    xyz_m [nant][3], s [..][3] -> [..][nant]"""
+    s = np.asarray(s, float)
+    ds = EARTH_RATE * np.stack([s[..., 1], -s[..., 0], np.zeros_like(s[..., 0])], axis=-1)
+    if unix is not None:
+        T = (float(unix) / 86400.0 + 2440587.5 - 2451545.0) / 36525.0
+        h = 1e-3                                         # centuries: P is a cubic in T, the difference exact to 10^-9 of it
+        dP = (precession_matrix(T + h) - precession_matrix(T - h)) / (2 * h * 36525.0 * 86400.0)
+        g = _r3(gmst_rad(unix))
+        ds = ds + s @ (g @ dP @ precession_matrix(T).T @ g.T).T
+    return antenna_delays(xyz_m, ds) * ROW_S
+
+
+def track_model(xyz_m, ra, dec, unix, clock_ns=None):
+    """The model of PbHandle.correlate_tracked for a J2000 position (radians) from `unix` on: float64 [nant][4] = delay0,
+    delay_rate, psi0, psi_rate with row 0 at `unix`.  The delays are antenna_delays' and antenna_delay_rates'; the
+    phases take the band as sampled from 384 MHz downwards, psi0 = -phase_turns(delay0) and psi_rate =
+    -phase_turns(delay_rate), which stops the fringe only if the signals arrive as "Phase mode" above describes: the sign
+    of that 384 MHz term is not known from the reference."""
+    s = source_vector(ra, dec, unix)
+    d0 = antenna_delays(xyz_m, s, clock_ns)
+    d1 = antenna_delay_rates(xyz_m, s, unix)
+    return np.stack([d0, d1, -phase_turns(d0), -phase_turns(d1)], axis=-1)
 
 
 def sky_grid(ra0, dec0, half_width_arcmin, n):
